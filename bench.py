@@ -11,6 +11,15 @@ HBM before the timed region.
   python bench.py --gpus N --steps K --warmup W [--workload c3|c2|c5|c5share|tiny|tinycg]
                    [--mode fast|exact]
                    [--scaling strong|weak]
+                   [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the line: `value`, `ms_per_step` and
+the accounting of the timed iterations themselves.  --full adds everything that takes runs or
+reads of its own: per-kernel times and rooflines, the 20-iteration cold run, the result check
+(and, N > 1, the other sharding and the per-rank clocks), the exact-mode line, the parity
+object and the CPU baseline.  --dump-outputs DIR (N = 1): after the timed steps, what the last
+one left for a caller -- per-individual log-likelihoods, indF, alpha, allele frequencies and a
+seeded sample of the posteriors -- as DIR/<name>.npy (float64).
 
 N > 1 = one rank per GPU over RCCL.  Started by torch.distributed.run (RANK / WORLD_SIZE in
 the environment) the process IS a rank; started plainly (`python bench.py --gpus N`) it
@@ -575,11 +584,13 @@ def allreduce(ctx, values, op="sum"):
 FAMILIES = ("emission", "forward", "backward", "lkl_batch", "est_maf", "lkl_first", "bfgs")
 
 
-def timed_loop(ctx, run, steps, warmup, replicas=()):
+def timed_loop(ctx, run, steps, warmup, replicas=(), counts=True):
     """W untimed iterations from the starting values, then EXACTLY K timed ones between
     barriers; MAX over ranks.  Every iteration's own wall time is kept as well (iter_EM returns
     after its stream has drained, so the clock reads add no synchronisation): the first
-    iterations of a run are its cold start (L-BFGS-B needs 18, 13, 6 objective rounds there)."""
+    iterations of a run are its cold start (L-BFGS-B needs 18, 13, 6 objective rounds there).
+    counts: fast mode's kernel-version and est_maf route counters over the timed iterations
+    (`regime`).  Fast mode's kernel-family times come from span_loop, run after this."""
     import threading
     em = run["em"]
 
@@ -617,7 +628,7 @@ def timed_loop(ctx, run, steps, warmup, replicas=()):
     em.reset_timing()
     # which kernel versions the objective rounds take and how many sites of the frequency step leave
     # its common route (include/nghmm_debug.h): counted over the timed iterations only
-    fast_handles = handles_of(em) if ctx.args.mode == "fast" else []
+    fast_handles = handles_of(em) if counts and ctx.args.mode == "fast" else []
     for h in fast_handles:
         h.mode_counts(reset=True)
         h.estmaf_counts(reset=True)
@@ -669,35 +680,98 @@ def timed_loop(ctx, run, steps, warmup, replicas=()):
             mode_counts[k] = mode_counts.get(k, 0) + v
         for k, v in h.estmaf_counts().items():
             estmaf_counts[k] = estmaf_counts.get(k, 0) + v
-    if not in_loop:
-        hs = handles_of(em) + list(replicas)
-        n_sp = max(1, min(5, steps))
-        saved_timing = dict(em.timing) if isinstance(getattr(em, "timing", None), dict) else None
-        saved_ex = (ex.calls, ex.bytes, ex.host_ms) if ex is not None and hasattr(ex, "calls") else None
-        for h in hs:
-            h.set_switch("spans", 1)
-        try:
-            for _ in range(n_sp):
-                iterate_all()
-                for k in fam:
-                    ms, n = em.hmm.kernel_ms(k)
-                    fam[k] += ms * steps / n_sp
-                    launches[k] += n * steps / n_sp
-        finally:
-            for h in hs:
-                h.set_switch("spans", 0)
-        # (the accounting of the timed region is what the line reports)
-        if saved_timing is not None:
-            em.timing.clear()
-            em.timing.update(saved_timing)
-        if saved_ex is not None:
-            ex.calls, ex.bytes, ex.host_ms = saved_ex
-            if hasattr(ex, "take_log"):
-                ctx.torch.cuda.synchronize()
-                ex.take_log()
     return dict(dt=dt, fam=fam, launches=launches, rounds=rounds, points=points, ind_rounds=ind_rounds,
                 ref_calls=ref_calls, each_ms=each_ms, each_rounds=each_rounds, steps=steps, warmup=warmup,
-                exchange_log=exchange_log, mode_counts=mode_counts, estmaf_counts=estmaf_counts)
+                exchange_log=exchange_log, mode_counts=mode_counts, estmaf_counts=estmaf_counts,
+                in_loop=in_loop)
+
+
+def span_loop(ctx, run, tl, replicas=()):
+    """Fast mode: the kernel-family times of the timed loop `tl` (it records none) from a few
+    iterations of the same steady state behind it with the switch `spans`, scaled to its K
+    iterations and added to tl's `fam` / `launches`; the timed region's own accounting is
+    restored afterwards.  Nothing to do where the timed iterations carried the events."""
+    if tl["in_loop"]:
+        return
+    em, steps, fam, launches = run["em"], tl["steps"], tl["fam"], tl["launches"]
+    ex = getattr(em, "exchange", None)
+    import threading
+
+    def iterate_all():
+        th = [threading.Thread(target=h.iter_EM) for h in replicas]
+        for t in th:
+            t.start()
+        em.iter_EM()
+        for t in th:
+            t.join()
+
+    hs = handles_of(em) + list(replicas)
+    n_sp = max(1, min(5, steps))
+    saved_timing = dict(em.timing) if isinstance(getattr(em, "timing", None), dict) else None
+    saved_ex = (ex.calls, ex.bytes, ex.host_ms) if ex is not None and hasattr(ex, "calls") else None
+    for h in hs:
+        h.set_switch("spans", 1)
+    try:
+        for _ in range(n_sp):
+            iterate_all()
+            for k in fam:
+                ms, n = em.hmm.kernel_ms(k)
+                fam[k] += ms * steps / n_sp
+                launches[k] += n * steps / n_sp
+    finally:
+        for h in hs:
+            h.set_switch("spans", 0)
+    # (the accounting of the timed region is what the line reports)
+    if saved_timing is not None:
+        em.timing.clear()
+        em.timing.update(saved_timing)
+    if saved_ex is not None:
+        ex.calls, ex.bytes, ex.host_ms = saved_ex
+        if hasattr(ex, "take_log"):
+            ctx.torch.cuda.synchronize()
+            ex.take_log()
+
+
+DUMP_SEED = 2024
+
+
+def dump_outputs(ctx, run, out_dir):
+    """--dump-outputs: what the timed path's last step left for its caller, as DIR/<name>.npy
+    (float64): the per-individual log-likelihoods of its E-step (`ind_lkl`), the M-step's `indF`
+    and `alpha`, the allele frequencies (`freq`) and the posteriors of the IBD state
+    (`marg_prob`, [sites][individuals]).  At most 64 MB in all: the posteriors are those of blocks
+    of 64 consecutive sites at seeded random offsets (`marg_prob_sites`: the site of each row, as
+    float64) when all of them would exceed 32 MB, and a frequency vector longer than
+    2^20 sites is a seeded random sample of them.  The sample depends on the shape only, so two
+    builds dump the same cells."""
+    import numpy as np
+    torch, em = ctx.torch, run["em"]
+    hmm = em.hmm
+    I, S = hmm.n_ind, hmm.n_sites
+    rng = np.random.default_rng(DUMP_SEED)
+    lkl = em.ind_lkl if getattr(em, "ind_lkl", None) is not None else hmm.ind_lkl
+    arrays = {"ind_lkl": np.array(lkl, dtype=np.float64), "indF": hmm.indF, "alpha": hmm.alpha}
+    freq = hmm.freq
+    if S > 1 << 20:
+        freq = freq[np.sort(rng.choice(S, 1 << 20, replace=False))]
+    arrays["freq"] = freq
+    blk, cap = 64, max(64, (32 << 20) // (8 * I))        # sites of posteriors within 32 MB
+    if S <= cap:
+        blk, starts = S, np.array([0])
+    else:
+        starts = np.sort(rng.choice(S // blk, cap // blk, replace=False)) * blk
+    buf = torch.empty((blk, I), dtype=torch.float64, device=ctx.device)
+    post = np.empty((len(starts) * blk, I))
+    for b, lo in enumerate(starts):
+        em.backend.pack_posteriors(int(lo), int(lo) + blk, buf)   # [site][individual], synchronised
+        post[b * blk:(b + 1) * blk] = buf.cpu().numpy()
+    arrays["marg_prob"] = post
+    arrays["marg_prob_sites"] = np.repeat(starts, blk).astype(np.float64) + np.tile(np.arange(blk), len(starts))
+    del buf
+    assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 def handles_of(em):
@@ -949,9 +1023,23 @@ def main():
                     default=float(os.environ.get("NGHMM_BENCH_TIMEOUT_S", "120")),
                     help="process-group timeout: a collective (or the rendezvous) that takes longer "
                          "ends the rank with a non-zero exit code")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline figure: per-kernel times and rooflines, the "
+                         "cold run, the result check, the other sharding (N > 1), the exact-mode line, "
+                         "the parity object and the CPU baseline (each --no_* option drops its part)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="N = 1: after the timed steps, write what the last one computed as "
+                         "DIR/<name>.npy (float64; a seeded sample of the posteriors and of long "
+                         "frequency vectors, at most 64 MB in all)")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
+    if args.dump_outputs and (args.gpus > 1 or args.emulate_ranks > 1):
+        raise SystemExit("--dump-outputs needs --gpus 1 and no --emulate_ranks")
+    if args.write_check and not args.full:
+        raise SystemExit("--write_check stores the result check, which --full computes")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         launch_ranks(args)       # does not return
     if args.gpus == 1:
@@ -1097,12 +1185,17 @@ def run_rank(args):
         for h in handles_of(em) + replicas:
             h.set_switch("no_bg_stream", 1)
             h.set_switch("spans", 1)
-    tl = timed_loop(ctx, run, args.steps, args.warmup, replicas)
+    full = args.full
+    tl = timed_loop(ctx, run, args.steps, args.warmup, replicas, counts=full)
+    if args.dump_outputs:
+        dump_outputs(ctx, run, args.dump_outputs)
+    if full:
+        span_loop(ctx, run, tl, replicas)
     dt, fam, launches = tl["dt"], tl["fam"], tl["launches"]
     rounds, points, ind_rounds, ref_calls = tl["rounds"], tl["points"], tl["ind_rounds"], tl["ref_calls"]
 
     per_rank = None
-    if world > 1:
+    if world > 1 and full:
         # every rank's own clocks, so that the scaling line can be read: kernel families
         # (HIP events on the library's stream), the exchange (duration and the part of it the
         # host actually waited for), the frequency step on the own site range
@@ -1116,13 +1209,13 @@ def run_rank(args):
     # other (fast mode overlaps them on two streams in the timed loop); after the timed loop's
     # accounting has been taken, before the check resets the parameters
     kt = None
-    if args.mode == "fast" and not args.serial_kernels and args.replicas == 1:
+    if full and args.mode == "fast" and not args.serial_kernels and args.replicas == 1:
         kt = serial_kernel_loop(ctx, run, max(1, min(5, args.steps)))
     cold = None
-    if args.mode == "fast" and args.replicas == 1 and V == 1 and not args.no_cold:
+    if full and args.mode == "fast" and args.replicas == 1 and V == 1 and not args.no_cold:
         cold = cold_run(ctx, run)
     check = None
-    if not args.no_check and V == 1:
+    if full and not args.no_check and V == 1:
         check = result_check(ctx, run)
     C_waves = em.hmm.layout()[0]
     for h in replicas:
@@ -1133,11 +1226,11 @@ def run_rank(args):
 
     # ---- N > 1, site shards: the same data set once more in the OTHER layout ----
     alt = None
-    if world > 1 and by_sites and not args.no_alt and args.scaling == "strong":
+    if full and world > 1 and by_sites and not args.no_alt and args.scaling == "strong":
         alt = alt_sharding(ctx, min(args.steps, 5), min(args.warmup, 2), check)
 
     exact_line = None
-    if (world == 1 and V == 1 and args.replicas == 1 and args.mode == "fast" and not args.no_exact_line
+    if (full and world == 1 and V == 1 and args.replicas == 1 and args.mode == "fast" and not args.no_exact_line
             and args.workload == "c3" and rank == 0):
         exact_line = exact_mode_line(ctx)
 
@@ -1156,175 +1249,12 @@ def run_rank(args):
         est_sites = S if by_sites else S / (world * V)       # what one rank's est_maf covers
         est_inds = I if by_sites else I_tot
         call_geno = ctx.call_geno
-        # dominant kernel family by measured time, and its algorithmic traffic per launch
-        # (DESIGN.md section 4); est_maf = 24 B GL + 8 B posterior per site-individual;
-        # fast mode: the first objective round of an iteration (all I individuals) reads the
-        # 16 B GL and writes the 8 B emission ratio + 4 B checkpoints; later rounds read 8 B per
-        # still-active individual; the E-step then reads 8 + 4 B and writes 8 B
-        fast = args.mode == "fast"
         glb = 0.25 if call_geno else 24.0     # bytes of genotype likelihoods per cell (est_maf)
         glq = 0.25 if call_geno else 16.0     # ... in the interleaved copy the forward walk reads
-        # ---- every kernel of the iteration against BOTH roofs; `bound` names its limiter ----
-        # times: HIP events on the library's stream around each kernel family (nghmm_kernel_ms)
-        pmc_summ, pmc_why = (pmc_summary() if (args.workload == "c3" and fast and world == 1 and V == 1 and
-                                               not args.n_ind and not args.n_sites)
-                             else (None, "PMC passes exist for the default workload on one GPU only"))
-        pmc = pmc_traffic(pmc_summ, I, C_waves)
-        isa, isa_path, isa_why = isa_counts()
-        rows = {}
-        n_first = launches["lkl_first"]
-        later_ms = fam["lkl_batch"] - fam["lkl_first"]
-        later_ind = max(ind_rounds_k - I * n_first, 0)
-        later_launches = max(launches["lkl_batch"] - n_first, 0)
-        if fast:
-            if n_first and fam["lkl_first"] > 0:
-                rows["lkl_first_round"] = dict(ms=fam["lkl_first"], launches=n_first,
-                                               bytes=(glq + 12.0) * S * I * n_first, sites_ind=S * I * n_first,
-                                               traffic=pmc.get("lkl_first_round_per_launch"))
-            if later_launches and later_ms > 0:
-                t = pmc.get("lkl_later_rounds_per_individual")
-                rows["lkl_later_rounds"] = dict(ms=later_ms, launches=later_launches,
-                                                bytes=8.0 * S * later_ind, sites_ind=S * later_ind,
-                                                traffic=t * later_ind / later_launches if t else None)
-            if launches["est_maf"] and fam["est_maf"] > 0:
-                t = pmc.get("est_maf_per_iteration")
-                rows["est_maf"] = dict(ms=fam["est_maf"], launches=launches["est_maf"],
-                                       bytes=(glb + 8.0) * est_sites * est_inds * launches["est_maf"],
-                                       sites=est_sites * launches["est_maf"], traffic=t)
-            if launches["forward"] and fam["forward"] > 0:
-                rows["backward_sweep"] = dict(ms=fam["forward"], launches=launches["forward"],
-                                              bytes=20.0 * S * I * launches["forward"],
-                                              traffic=pmc.get("backward_sweep_per_iteration"))
-        roof_all = {}
-        for name, r in rows.items():
-            meta = KERNELS[name]
-            secs = r["ms"] * 1e-3
-            gbs = r["bytes"] / secs / 1e9
-            e = {"bound": meta["bound"], "kernel": meta["kernel"],
-                 "ms_per_em_iteration": r["ms"] / K_k, "launches": r["launches"],
-                 "avg_launch_ms": r["ms"] / r["launches"],
-                 "hbm": {"achieved_GBps": gbs, "peak_GBps": HBM_PEAK_GBS, "frac": gbs / HBM_PEAK_GBS,
-                         "algorithmic_bytes_per_launch": r["bytes"] / r["launches"],
-                         "traffic_bytes_per_launch": r["traffic"]},
-                 "note": meta["note"]}
-            w_valu = w_fp64 = None
-            blocks = (isa or {}).get(name)
-            if name == "est_maf" and blocks:
-                vf = estmaf_instr_per_site(est_inds, (isa or {}).get("est_maf:model"))
-                if vf:
-                    per = {"valu": vf[0], "fp64": vf[1],
-                           "what": "from the assembly's parts: an upper bound (the build decision's "
-                                   "block is counted with every exact pass)"}
-                    # the counted instructions of this build's PMC pass, when there is one: the
-                    # assembly model then only supplies the FP64 share
-                    k = (pmc_summ or {}).get("k_fast_estmaf<16, 64, true>")
-                    if k and k.get("insts_valu_per_launch") and k.get("avg_grid_threads") and est_inds == 1000:
-                        v_pmc = k["insts_valu_per_launch"] / (k["avg_grid_threads"] / 64.0)
-                        per = {"valu": v_pmc, "fp64": vf[1] * v_pmc / vf[0], "assembly_model_valu": vf[0],
-                               "what": f"VALU: SQ_INSTS_VALU per site of this build's PMC pass ({PMC_SUMMARY}); "
-                                       "FP64: that count times the FP64 share of the assembly's parts"}
-                    w_valu, w_fp64 = per["valu"] * r["sites"], per["fp64"] * r["sites"]
-            elif meta.get("isa") and blocks:
-                v, f = walk_instr_per_site(blocks)
-                w_valu, w_fp64, per = v * r["sites_ind"] / 64.0, f * r["sites_ind"] / 64.0, {"valu": v, "fp64": f}
-            if w_valu:
-                e["fp64_valu"] = {"achieved_wave_instr_per_s": w_fp64 / secs, "peak": FP64_ISSUE_PEAK,
-                                  "frac": w_fp64 / secs / FP64_ISSUE_PEAK,
-                                  "valu_issue_frac": w_valu / secs / FP64_ISSUE_PEAK,
-                                  "instr_per_site": per,
-                                  "source": f"{isa_path} (device assembly of this build, id {this_build_id()})"}
-            elif meta["bound"] == "fp64_valu":
-                e["fp64_valu"] = {"achieved_wave_instr_per_s": None, "peak": FP64_ISSUE_PEAK, "frac": None,
-                                  "instr_per_site": None,
-                                  "reason": isa_why or f"{isa_path}: no blocks for this kernel"}
-            roof_all[name] = e
-        # the iteration as a whole (north_star: "as fraction of HBM roofline"): algorithmic bytes and
-        # FP64 wave-instructions of its four kernels per EM iteration against the TIMED loop's
-        # iteration (wall clock, everything in it), next to the kernels' own sum
-        roof_iter = None
-        if fast and roof_all:
-            it_bytes = sum(r["bytes"] for r in rows.values()) / K_k
-            it_traffic = [roof_all[n]["hbm"]["traffic_bytes_per_launch"] for n in rows]
-            it_traffic = (sum(t * rows[n]["launches"] for t, n in zip(it_traffic, rows)) / K_k
-                          if all(t is not None for t in it_traffic) else None)
-            it_fp64 = [roof_all[n].get("fp64_valu", {}).get("achieved_wave_instr_per_s") for n in rows
-                       if roof_all[n]["bound"] == "fp64_valu" or "fp64_valu" in roof_all[n]]
-            it_fp64 = (sum(roof_all[n]["fp64_valu"]["achieved_wave_instr_per_s"] * rows[n]["ms"] * 1e-3
-                           for n in rows if roof_all[n].get("fp64_valu", {}).get("achieved_wave_instr_per_s")) / K_k
-                       if it_fp64 and all(v is not None for v in it_fp64) else None)
-            wall_s = dt / K
-            roof_iter = {"ms_per_em_iteration": wall_s * 1e3,
-                         "kernels_ms_per_em_iteration": sum(r["ms"] for r in rows.values()) / K_k,
-                         "algorithmic_bytes_per_em_iteration": it_bytes,
-                         "traffic_bytes_per_em_iteration": it_traffic,
-                         "hbm": {"achieved_GBps": it_bytes / wall_s / 1e9, "peak_GBps": HBM_PEAK_GBS,
-                                 "frac": it_bytes / wall_s / 1e9 / HBM_PEAK_GBS},
-                         "fp64_valu": ({"achieved_wave_instr_per_s": it_fp64 / wall_s, "peak": FP64_ISSUE_PEAK,
-                                        "frac": it_fp64 / wall_s / FP64_ISSUE_PEAK,
-                                        "wave_instr_per_em_iteration": it_fp64}
-                                       if it_fp64 else None),
-                         "note": "the four kernels of roofline_all_kernels (objective rounds first / later, est_maf, "
-                                 "backward sweep) per EM iteration of THIS line's timed loop; the backward sweep's "
-                                 "instructions are not counted (HBM-bound: no assembly block model for it)"}
-        if not fast:   # exact mode: latency-bound chains, not a roofline candidate
-            for k in ("forward", "backward", "lkl_batch", "est_maf"):
-                if launches[k] and fam[k] > 0:
-                    roof_all[k] = {"bound": "latency", "ms_per_em_iteration": fam[k] / K,
-                                   "launches": launches[k]}
-        # the contract's object: the kernel that takes the most time, against ITS roof
-        dom = max(roof_all, key=lambda k: roof_all[k]["ms_per_em_iteration"]) if roof_all else None
-        if dom and roof_all[dom]["bound"] == "fp64_valu" and roof_all[dom]["fp64_valu"]["frac"] is None:
-            # no instruction counts for this build: the dominant kernel against the HBM roof only
-            d = roof_all[dom]
-            roofline = {"bound": "hbm", "kernel": dom, "achieved": d["hbm"]["achieved_GBps"],
-                        "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": d["hbm"]["frac"],
-                        "traffic": d["hbm"]["traffic_bytes_per_launch"],
-                        "algorithmic_bytes_per_launch": d["hbm"]["algorithmic_bytes_per_launch"],
-                        "avg_launch_ms": d["avg_launch_ms"], "launches": d["launches"],
-                        "device_kernel": d["kernel"],
-                        "note": "this kernel is FP64-issue bound (DESIGN.md section 4), but "
-                                + d["fp64_valu"]["reason"] + ": only its HBM fraction can be stated"}
-        elif dom and roof_all[dom]["bound"] == "fp64_valu":
-            d = roof_all[dom]
-            roofline = {"bound": "fp64_valu", "kernel": dom, "achieved": d["fp64_valu"]["achieved_wave_instr_per_s"],
-                        "peak": FP64_ISSUE_PEAK, "unit": "FP64 wave-instructions/s",
-                        "frac": d["fp64_valu"]["frac"],
-                        "valu_issue_frac": d["fp64_valu"]["valu_issue_frac"],
-                        "hbm_frac": d["hbm"]["frac"], "hbm_achieved_GBps": d["hbm"]["achieved_GBps"],
-                        "traffic": d["hbm"]["traffic_bytes_per_launch"],
-                        "algorithmic_bytes_per_launch": d["hbm"]["algorithmic_bytes_per_launch"],
-                        "avg_launch_ms": d["avg_launch_ms"], "launches": d["launches"],
-                        "device_kernel": d["kernel"], "note": d["note"]}
-        elif dom and roof_all[dom]["bound"] == "hbm":
-            d = roof_all[dom]
-            roofline = {"bound": "hbm", "kernel": dom, "achieved": d["hbm"]["achieved_GBps"],
-                        "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": d["hbm"]["frac"],
-                        "traffic": d["hbm"]["traffic_bytes_per_launch"],
-                        "algorithmic_bytes_per_launch": d["hbm"]["algorithmic_bytes_per_launch"],
-                        "avg_launch_ms": d["avg_launch_ms"], "launches": d["launches"],
-                        "device_kernel": d["kernel"], "note": d["note"]}
-        else:
-            roofline = {"bound": "latency", "kernel": dom, "achieved": None, "peak": None, "unit": None,
-                        "frac": None, "traffic": None,
-                        "note": "exact mode: sequential log-space chains (DESIGN.md section 4)"}
-        if roofline.get("traffic") is not None:
-            roofline["traffic_source"] = (f"{PMC_SUMMARY}: rocprofv3 --pmc FETCH_SIZE / "
-                                          f"WRITE_SIZE passes of this workload and THIS build (id "
-                                          f"{this_build_id()}, profiles/collect.sh), not measured in this run")
-        else:
-            roofline["traffic_source"] = pmc_why
-        roofline["kernel_times"] = (
-            f"HIP events over {K_k} iterations that follow the timed loop with the library's switch "
-            "no_bg_stream (every kernel alone on the chip; in the timed loop the backward sweep and "
-            "est_maf run on a second stream next to the objective rounds and the spans overlap)"
-            if kt is not None else
-            ("HIP events over the timed loop" if (args.mode != "fast" or args.serial_kernels) else
-             f"HIP events over {max(1, min(5, args.steps))} iterations that follow the timed loop (fast mode "
-             "records them on request only, switch `spans`: the timed iterations carry none)"))
-        roofline["timed_loop"] = ("no timing events inside the timed iterations (fast mode; switch `spans` off): "
-                                  "`per_step_kernel_ms_timed_loop` comes from iterations behind them, two streams "
-                                  "as in the timed loop" if (args.mode == "fast" and not args.serial_kernels) else
-                                  "timing events inside the timed iterations")
+        roofline = roof_all = roof_iter = None
+        if full:
+            roofline, roof_all, roof_iter = kernel_rooflines(ctx, fam, launches, ind_rounds_k, K_k, K, dt, I, S,
+                                                             est_sites, est_inds, glq, glb, C_waves, kt)
         each = tl["each_ms"]
         n_run = min(20, len(each))
         vs_n1 = None
@@ -1355,6 +1285,9 @@ def run_rank(args):
             "warmup": args.warmup,
             "ms_per_step": dt / K * 1e3,
             "higher_is_better": True,
+            # a plain run: the headline and the timed loop's own accounting; the objects below that
+            # take runs or reads of their own are null there and filled by --full
+            "full": full,
             # total work fixed as N grows (strong: this run is a point of the 1/2/4/8 series
             # over the same 1000 x 1M job) or per-GPU work fixed (weak)
             "scaling": args.scaling,
@@ -1385,8 +1318,9 @@ def run_rank(args):
             "roofline": roofline,
             "roofline_all_kernels": roof_all,
             "roofline_iteration": roof_iter,
-            "per_step_kernel_ms": {k: fam[k] / K_k for k in fam if k != "lkl_first"},
-            "per_step_kernel_ms_timed_loop": {k: fam_timed[k] / K for k in fam_timed if k != "lkl_first"},
+            "per_step_kernel_ms": {k: fam[k] / K_k for k in fam if k != "lkl_first"} if full else None,
+            "per_step_kernel_ms_timed_loop": ({k: fam_timed[k] / K for k in fam_timed if k != "lkl_first"}
+                                              if full else None),
             # the metric is EM iterations/s and a run is >= 10 iterations from the starting values
             # (parse_args.cpp:5-34 min_iters 10): `ms_per_step` is the steady state after the
             # warm-up iterations, these are the run's first iterations themselves
@@ -1404,7 +1338,7 @@ def run_rank(args):
             "vs_n1": vs_n1,
             "alt_sharding": alt,
             "exact_mode": exact_line,
-            "parity": parity_object(),
+            "parity": parity_object() if full else None,
             "predicted": (None if V == 1 else {
                 "emulated_rank_of": V,
                 "shard": "sites" if by_sites else "individuals",
@@ -1435,7 +1369,7 @@ def run_rank(args):
                      "bytes leaving each GPU per EM iteration: posterior slices to the other "
                      "ranks' site ranges (all-to-all, issued right after the E-step, under the "
                      "remaining objective rounds) and the own frequencies (all-gather)")),
-            "exchange_ms": (None if world == 1 else {
+            "exchange_ms": (None if per_rank is None else {
                 k: max(r["exchange_ms_per_iter"][k] for r in per_rank)
                 for k in per_rank[0]["exchange_ms_per_iter"]}),
             "per_rank": per_rank,
@@ -1445,12 +1379,188 @@ def run_rank(args):
                      "ind_rounds_per_iter": ind_rounds / K,
                      "reference_forward_passes_per_ind_iter": ref_calls / (K * I)},
         }
-        if not args.no_cpu_baseline and world == 1:   # on rank 0 at N = 1 only
+        if full and not args.no_cpu_baseline and world == 1:   # on rank 0 at N = 1 only
             out["cpu_baseline"] = cpu_baseline(pkg, full_c2=args.cpu_full_c2, wl=wl)
         print(json.dumps(out))
         sys.stdout.flush()
     if world > 1 or args.emulate_rccl:
         dist.destroy_process_group()
+
+
+def kernel_rooflines(ctx, fam, launches, ind_rounds_k, K_k, K, dt, I, S, est_sites, est_inds, glq, glb,
+                     C_waves, kt):
+    """--full: every kernel of the iteration against both roofs (`roofline_all_kernels`), the one
+    that takes the most time against its own (`roofline`) and the iteration as a whole
+    (`roofline_iteration`), from the kernel-family times `fam` / `launches` over K_k iterations."""
+    args, world, V = ctx.args, ctx.world, ctx.args.emulate_ranks
+    fast = args.mode == "fast"
+    # dominant kernel family by measured time, and its algorithmic traffic per launch
+    # (DESIGN.md section 4); est_maf = 24 B GL + 8 B posterior per site-individual;
+    # fast mode: the first objective round of an iteration (all I individuals) reads the
+    # 16 B GL and writes the 8 B emission ratio + 4 B checkpoints; later rounds read 8 B per
+    # still-active individual; the E-step then reads 8 + 4 B and writes 8 B
+    # ---- every kernel of the iteration against BOTH roofs; `bound` names its limiter ----
+    # times: HIP events on the library's stream around each kernel family (nghmm_kernel_ms)
+    pmc_summ, pmc_why = (pmc_summary() if (args.workload == "c3" and fast and world == 1 and V == 1 and
+                                           not args.n_ind and not args.n_sites)
+                         else (None, "PMC passes exist for the default workload on one GPU only"))
+    pmc = pmc_traffic(pmc_summ, I, C_waves)
+    isa, isa_path, isa_why = isa_counts()
+    rows = {}
+    n_first = launches["lkl_first"]
+    later_ms = fam["lkl_batch"] - fam["lkl_first"]
+    later_ind = max(ind_rounds_k - I * n_first, 0)
+    later_launches = max(launches["lkl_batch"] - n_first, 0)
+    if fast:
+        if n_first and fam["lkl_first"] > 0:
+            rows["lkl_first_round"] = dict(ms=fam["lkl_first"], launches=n_first,
+                                           bytes=(glq + 12.0) * S * I * n_first, sites_ind=S * I * n_first,
+                                           traffic=pmc.get("lkl_first_round_per_launch"))
+        if later_launches and later_ms > 0:
+            t = pmc.get("lkl_later_rounds_per_individual")
+            rows["lkl_later_rounds"] = dict(ms=later_ms, launches=later_launches,
+                                            bytes=8.0 * S * later_ind, sites_ind=S * later_ind,
+                                            traffic=t * later_ind / later_launches if t else None)
+        if launches["est_maf"] and fam["est_maf"] > 0:
+            t = pmc.get("est_maf_per_iteration")
+            rows["est_maf"] = dict(ms=fam["est_maf"], launches=launches["est_maf"],
+                                   bytes=(glb + 8.0) * est_sites * est_inds * launches["est_maf"],
+                                   sites=est_sites * launches["est_maf"], traffic=t)
+        if launches["forward"] and fam["forward"] > 0:
+            rows["backward_sweep"] = dict(ms=fam["forward"], launches=launches["forward"],
+                                          bytes=20.0 * S * I * launches["forward"],
+                                          traffic=pmc.get("backward_sweep_per_iteration"))
+    roof_all = {}
+    for name, r in rows.items():
+        meta = KERNELS[name]
+        secs = r["ms"] * 1e-3
+        gbs = r["bytes"] / secs / 1e9
+        e = {"bound": meta["bound"], "kernel": meta["kernel"],
+             "ms_per_em_iteration": r["ms"] / K_k, "launches": r["launches"],
+             "avg_launch_ms": r["ms"] / r["launches"],
+             "hbm": {"achieved_GBps": gbs, "peak_GBps": HBM_PEAK_GBS, "frac": gbs / HBM_PEAK_GBS,
+                     "algorithmic_bytes_per_launch": r["bytes"] / r["launches"],
+                     "traffic_bytes_per_launch": r["traffic"]},
+             "note": meta["note"]}
+        w_valu = w_fp64 = None
+        blocks = (isa or {}).get(name)
+        if name == "est_maf" and blocks:
+            vf = estmaf_instr_per_site(est_inds, (isa or {}).get("est_maf:model"))
+            if vf:
+                per = {"valu": vf[0], "fp64": vf[1],
+                       "what": "from the assembly's parts: an upper bound (the build decision's "
+                               "block is counted with every exact pass)"}
+                # the counted instructions of this build's PMC pass, when there is one: the
+                # assembly model then only supplies the FP64 share
+                k = (pmc_summ or {}).get("k_fast_estmaf<16, 64, true>")
+                if k and k.get("insts_valu_per_launch") and k.get("avg_grid_threads") and est_inds == 1000:
+                    v_pmc = k["insts_valu_per_launch"] / (k["avg_grid_threads"] / 64.0)
+                    per = {"valu": v_pmc, "fp64": vf[1] * v_pmc / vf[0], "assembly_model_valu": vf[0],
+                           "what": f"VALU: SQ_INSTS_VALU per site of this build's PMC pass ({PMC_SUMMARY}); "
+                                   "FP64: that count times the FP64 share of the assembly's parts"}
+                w_valu, w_fp64 = per["valu"] * r["sites"], per["fp64"] * r["sites"]
+        elif meta.get("isa") and blocks:
+            v, f = walk_instr_per_site(blocks)
+            w_valu, w_fp64, per = v * r["sites_ind"] / 64.0, f * r["sites_ind"] / 64.0, {"valu": v, "fp64": f}
+        if w_valu:
+            e["fp64_valu"] = {"achieved_wave_instr_per_s": w_fp64 / secs, "peak": FP64_ISSUE_PEAK,
+                              "frac": w_fp64 / secs / FP64_ISSUE_PEAK,
+                              "valu_issue_frac": w_valu / secs / FP64_ISSUE_PEAK,
+                              "instr_per_site": per,
+                              "source": f"{isa_path} (device assembly of this build, id {this_build_id()})"}
+        elif meta["bound"] == "fp64_valu":
+            e["fp64_valu"] = {"achieved_wave_instr_per_s": None, "peak": FP64_ISSUE_PEAK, "frac": None,
+                              "instr_per_site": None,
+                              "reason": isa_why or f"{isa_path}: no blocks for this kernel"}
+        roof_all[name] = e
+    # the iteration as a whole (north_star: "as fraction of HBM roofline"): algorithmic bytes and
+    # FP64 wave-instructions of its four kernels per EM iteration against the TIMED loop's
+    # iteration (wall clock, everything in it), next to the kernels' own sum
+    roof_iter = None
+    if fast and roof_all:
+        it_bytes = sum(r["bytes"] for r in rows.values()) / K_k
+        it_traffic = [roof_all[n]["hbm"]["traffic_bytes_per_launch"] for n in rows]
+        it_traffic = (sum(t * rows[n]["launches"] for t, n in zip(it_traffic, rows)) / K_k
+                      if all(t is not None for t in it_traffic) else None)
+        it_fp64 = [roof_all[n].get("fp64_valu", {}).get("achieved_wave_instr_per_s") for n in rows
+                   if roof_all[n]["bound"] == "fp64_valu" or "fp64_valu" in roof_all[n]]
+        it_fp64 = (sum(roof_all[n]["fp64_valu"]["achieved_wave_instr_per_s"] * rows[n]["ms"] * 1e-3
+                       for n in rows if roof_all[n].get("fp64_valu", {}).get("achieved_wave_instr_per_s")) / K_k
+                   if it_fp64 and all(v is not None for v in it_fp64) else None)
+        wall_s = dt / K
+        roof_iter = {"ms_per_em_iteration": wall_s * 1e3,
+                     "kernels_ms_per_em_iteration": sum(r["ms"] for r in rows.values()) / K_k,
+                     "algorithmic_bytes_per_em_iteration": it_bytes,
+                     "traffic_bytes_per_em_iteration": it_traffic,
+                     "hbm": {"achieved_GBps": it_bytes / wall_s / 1e9, "peak_GBps": HBM_PEAK_GBS,
+                             "frac": it_bytes / wall_s / 1e9 / HBM_PEAK_GBS},
+                     "fp64_valu": ({"achieved_wave_instr_per_s": it_fp64 / wall_s, "peak": FP64_ISSUE_PEAK,
+                                    "frac": it_fp64 / wall_s / FP64_ISSUE_PEAK,
+                                    "wave_instr_per_em_iteration": it_fp64}
+                                   if it_fp64 else None),
+                     "note": "the four kernels of roofline_all_kernels (objective rounds first / later, est_maf, "
+                             "backward sweep) per EM iteration of THIS line's timed loop; the backward sweep's "
+                             "instructions are not counted (HBM-bound: no assembly block model for it)"}
+    if not fast:   # exact mode: latency-bound chains, not a roofline candidate (DESIGN.md section 4)
+        for k in ("forward", "backward", "lkl_batch", "est_maf"):
+            if launches[k] and fam[k] > 0:
+                roof_all[k] = {"bound": "latency", "ms_per_em_iteration": fam[k] / K,
+                               "launches": launches[k]}
+    # the contract's object: the kernel that takes the most time, against ITS roof
+    dom = max(roof_all, key=lambda k: roof_all[k]["ms_per_em_iteration"]) if roof_all else None
+    if dom and roof_all[dom]["bound"] == "fp64_valu" and roof_all[dom]["fp64_valu"]["frac"] is None:
+        # no instruction counts for this build: the dominant kernel against the HBM roof only
+        d = roof_all[dom]
+        roofline = {"bound": "hbm", "kernel": dom, "achieved": d["hbm"]["achieved_GBps"],
+                    "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": d["hbm"]["frac"],
+                    "traffic": d["hbm"]["traffic_bytes_per_launch"],
+                    "algorithmic_bytes_per_launch": d["hbm"]["algorithmic_bytes_per_launch"],
+                    "avg_launch_ms": d["avg_launch_ms"], "launches": d["launches"],
+                    "device_kernel": d["kernel"],
+                    "note": "this kernel is FP64-issue bound (DESIGN.md section 4), but "
+                            + d["fp64_valu"]["reason"] + ": only its HBM fraction can be stated"}
+    elif dom and roof_all[dom]["bound"] == "fp64_valu":
+        d = roof_all[dom]
+        roofline = {"bound": "fp64_valu", "kernel": dom, "achieved": d["fp64_valu"]["achieved_wave_instr_per_s"],
+                    "peak": FP64_ISSUE_PEAK, "unit": "FP64 wave-instructions/s",
+                    "frac": d["fp64_valu"]["frac"],
+                    "valu_issue_frac": d["fp64_valu"]["valu_issue_frac"],
+                    "hbm_frac": d["hbm"]["frac"], "hbm_achieved_GBps": d["hbm"]["achieved_GBps"],
+                    "traffic": d["hbm"]["traffic_bytes_per_launch"],
+                    "algorithmic_bytes_per_launch": d["hbm"]["algorithmic_bytes_per_launch"],
+                    "avg_launch_ms": d["avg_launch_ms"], "launches": d["launches"],
+                    "device_kernel": d["kernel"], "note": d["note"]}
+    elif dom and roof_all[dom]["bound"] == "hbm":
+        d = roof_all[dom]
+        roofline = {"bound": "hbm", "kernel": dom, "achieved": d["hbm"]["achieved_GBps"],
+                    "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": d["hbm"]["frac"],
+                    "traffic": d["hbm"]["traffic_bytes_per_launch"],
+                    "algorithmic_bytes_per_launch": d["hbm"]["algorithmic_bytes_per_launch"],
+                    "avg_launch_ms": d["avg_launch_ms"], "launches": d["launches"],
+                    "device_kernel": d["kernel"], "note": d["note"]}
+    else:
+        roofline = {"bound": "latency", "kernel": dom, "achieved": None, "peak": None, "unit": None,
+                    "frac": None, "traffic": None,
+                    "note": "exact mode: sequential log-space chains (DESIGN.md section 4)"}
+    if roofline.get("traffic") is not None:
+        roofline["traffic_source"] = (f"{PMC_SUMMARY}: rocprofv3 --pmc FETCH_SIZE / "
+                                      f"WRITE_SIZE passes of this workload and THIS build (id "
+                                      f"{this_build_id()}, profiles/collect.sh), not measured in this run")
+    else:
+        roofline["traffic_source"] = pmc_why
+    roofline["kernel_times"] = (
+        f"HIP events over {K_k} iterations that follow the timed loop with the library's switch "
+        "no_bg_stream (every kernel alone on the chip; in the timed loop the backward sweep and "
+        "est_maf run on a second stream next to the objective rounds and the spans overlap)"
+        if kt is not None else
+        ("HIP events over the timed loop" if (args.mode != "fast" or args.serial_kernels) else
+         f"HIP events over {max(1, min(5, args.steps))} iterations that follow the timed loop (fast mode "
+         "records them on request only, switch `spans`: the timed iterations carry none)"))
+    roofline["timed_loop"] = ("no timing events inside the timed iterations (fast mode; switch `spans` off): "
+                              "`per_step_kernel_ms_timed_loop` comes from iterations behind them, two streams "
+                              "as in the timed loop" if (args.mode == "fast" and not args.serial_kernels) else
+                              "timing events inside the timed iterations")
+    return roofline, roof_all, roof_iter
 
 
 def cold20_object(cold, units_per_iter, I, S, glq, glb, est_sites, est_inds):
@@ -1610,6 +1720,7 @@ def alt_sharding(ctx, steps, warmup, main_check):
         return out
     em = run["em"]
     tl = timed_loop(ctx, run, steps, warmup)
+    span_loop(ctx, run, tl)
     K = max(steps, 1)
     per_rank = [None] * ctx.world
     dist.all_gather_object(per_rank, rank_clocks(ctx, run, tl))

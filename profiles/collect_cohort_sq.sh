@@ -9,7 +9,7 @@ OUT=gpurun_out/c5k_sq
 rm -rf $OUT
 timeout -k 10 300 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_ACTIVE_INST_VALU SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_INSTS_VALU \
   GRBM_GUI_ACTIVE SQ_ACTIVE_INST_ANY SQ_BUSY_CYCLES --output-format csv -d $OUT -o sq -- python3 bench.py \
-  --workload c5k --steps 2 --warmup 1 --no_cpu_baseline --no_exact_line --no_check --no_cold --serial_kernels \
+  --workload c5k --full --steps 2 --warmup 1 --no_cpu_baseline --no_exact_line --no_check --no_cold --serial_kernels \
   > /dev/null 2> gpurun_out/c5k_sq.err
 python3 - $TAG <<'PY'
 import csv, glob, collections, json, re, sys

@@ -9,7 +9,7 @@ OUT=gpurun_out/planning_sq
 rm -rf $OUT
 timeout -k 10 300 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAVES SQ_WAVE_CYCLES SQ_INSTS_SMEM \
   SQ_WAIT_INST_ANY SQ_ACTIVE_INST_VALU --output-format csv -d $OUT -o a -- python3 bench.py --workload c2 \
-  --steps 10 --warmup 6 --no_cpu_baseline --no_exact_line --no_check --no_cold --serial_kernels \
+  --full --steps 10 --warmup 6 --no_cpu_baseline --no_exact_line --no_check --no_cold --serial_kernels \
   > /dev/null 2> gpurun_out/planning_sq.err
 python3 - $TAG <<'PY'
 import csv, glob, collections, json, sys, statistics

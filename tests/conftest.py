@@ -2,10 +2,9 @@
 
 CPU tests (`-m "not gpu"`) cover the oracle, the host logic and the C-ABI surface;
 GPU tests (`-m gpu`) are the parity tests proper and call through the C ABI.
-Nothing here reads /root/reference at run time on the GPU box: the reference's
-L-BFGS-B object (oracle/_ref/libref_bfgs.so) is prebuilt by __graft_entry__.build()
-in the authoring container and travels with the snapshot; tests that need it skip
-when it is absent.
+Nothing here reads the reference at run time: what its own L-BFGS-B object
+(oracle/_ref/libref_bfgs.so) computes on the tests' cases is stored in
+tests/golden/ref_bfgs.npz (tests/golden/make_golden.py).
 """
 import importlib
 import os
@@ -43,11 +42,10 @@ def orc_det():
 
 
 @pytest.fixture(scope="session")
-def ref_bfgs():
-    import orclib
-    if not orclib.RefBfgs.available():
-        pytest.skip("oracle/_ref/libref_bfgs.so not built (needs /root/reference at build time)")
-    return orclib.RefBfgs()
+def ref_golden():
+    """The reference's own L-BFGS-B object on the cases of test_lbfgsb_ref.py and
+    test_host_logic.py, as stored by tests/golden/make_golden.py."""
+    return dict(np.load(os.path.join(ROOT, "tests", "golden", "ref_bfgs.npz")))
 
 
 @pytest.fixture(scope="session")

@@ -1,6 +1,7 @@
 """Generates tests/golden/*.npz: small seeded inputs and the outputs of the CPU oracle
 (both builds; the libm build run with the REFERENCE'S OWN optimizer object from
-oracle/_ref when it is available).  Run from the repo root:
+oracle/_ref when it is available), and (ref_bfgs.npz, which needs that object) what the
+reference's optimizer computes on the L-BFGS-B tests' cases.  Run from the repo root:
 
     python tests/golden/make_golden.py
 
@@ -47,6 +48,34 @@ def em_fixture(name, n_ind, n_sites, iters, **sim):
     print("wrote", path, os.path.getsize(path), "bytes")
 
 
+def ref_bfgs_fixture(name):
+    """The reference's own L-BFGS-B object (oracle/_ref/libref_bfgs.so, which oracle/Makefile
+    builds where the reference sources are at hand) on the cases of tests/test_lbfgsb_ref.py and
+    tests/test_host_logic.py: every evaluation point, final x and return value of the traced
+    cases, and on tests/conftest.py's `small_sim` the per-individual optima and three EM
+    iterations with it plugged into the oracle."""
+    import test_host_logic
+    import test_lbfgsb_ref as T
+    ref, orc = orclib.RefBfgs(), orclib.Oracle("libm")
+    out = {}
+    for case, (fn, x0, lb, ub) in T.golden_cases().items():
+        x, r, trace = T.run_traced(ref.findmax, fn, x0, lb, ub)
+        out.update({case + "_x": x, case + "_r": np.float64(r), case + "_trace": np.array(trace)})
+    # tests/conftest.py: small_sim
+    d = pkg.simulate.simulate(10, 600, seed=4242, n_chrom=2, missing_rate=0.05, indF="r", alpha=0.5,
+                              freq="r")
+    gl = pkg.simulate.normalise_log_gl(d.gl)
+    out["small_sim_gl_sum"] = np.float64(gl.sum())
+    out["hmm_x"], out["hmm_r"], out["hmm_calls"] = T.hmm_objective_runs(ref.findmax, orc, d, gl)
+    for k, v in T.em_state(orc, d, gl, ref).items():
+        out["em_" + k] = v
+    out["batched_x"] = test_host_logic.scalar_runs_from_03_005(orc, ref.findmax, d, gl)
+    path = os.path.join(ROOT, "tests", "golden", name)
+    np.savez_compressed(path, **out)
+    print("wrote", path, os.path.getsize(path), "bytes")
+
+
 if __name__ == "__main__":
     orclib.build_oracle()
     em_fixture("em_small.npz", 8, 300, 3, seed=2024, n_chrom=2, missing_rate=0.05)
+    ref_bfgs_fixture("ref_bfgs.npz")

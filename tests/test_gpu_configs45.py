@@ -278,7 +278,7 @@ def test_bench_four_ranks_on_the_full_workload_reproduce_the_one_gpu_job(pkg):
 
     def run(*extra):
         cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "c3", "--steps", "2",
-               "--warmup", "1", "--no_cpu_baseline", "--no_exact_line", *extra]
+               "--warmup", "1", "--full", "--no_cpu_baseline", "--no_exact_line", *extra]
         r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=1500, cwd=ROOT)
         assert r.returncode == 0, r.stderr[-3000:]
         return json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
@@ -343,7 +343,7 @@ def test_bench_config5_shape_ranks_reproduce_the_one_gpu_job(pkg, ranks, n_sites
 
     def run(*extra):
         cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "c5", "--n_sites", str(n_sites),
-               "--steps", "2", "--warmup", "1", "--no_cpu_baseline", *extra]
+               "--steps", "2", "--warmup", "1", "--full", "--no_cpu_baseline", *extra]
         r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
         assert r.returncode == 0, r.stderr[-3000:]
         return json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])

@@ -89,7 +89,7 @@ def test_bench_multi_rank_path_on_one_gpu(pkg):
 
     def run(*extra, workload="tiny"):
         cmd = [sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1",
-               "--workload", workload, "--no_cpu_baseline", *extra]
+               "--workload", workload, "--full", "--no_cpu_baseline", *extra]
         r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=root)
         assert r.returncode == 0, r.stderr[-2000:]
         return json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])

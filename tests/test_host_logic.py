@@ -54,10 +54,23 @@ def test_batched_bfgs_equals_blocking_findmax(pkg, orc_libm, small_sim, fixed):
     assert st.rounds >= 2
 
 
-def test_batched_bfgs_against_reference_object(pkg, orc_libm, ref_bfgs, small_sim):
-    """Same, against the reference's own compiled findmax_bfgs."""
+def scalar_runs_from_03_005(orc, impl, d, gl):
+    """A blocking findmax_bfgs `impl` per individual of `d` from (0.3, 0.05), the emissions of
+    (0.3, 0.05, 0.2): final (indF, alpha) [I][2]."""
+    em = orclib.OracleEM(orc, gl, d.pos_dist_mb)
+    em.set_params(0.3, 0.05, 0.2)
+    em.init_emission()
+    e = em.e_prob
+    pos = np.ascontiguousarray(d.pos_dist_mb)
+    return np.array([_scalar_findmax(orc, impl, e[i], pos, [0.3, 0.05])[0] for i in range(d.n_ind)])
+
+
+def test_batched_bfgs_against_reference_object(pkg, orc_libm, ref_golden, small_sim):
+    """Same, against the reference's own compiled findmax_bfgs (its results on this data:
+    tests/golden/ref_bfgs.npz, tests/golden/make_golden.py)."""
     hm = importlib.import_module("ngsf-hmm_amd.hmm")
     d, gl = small_sim
+    assert gl.sum() == ref_golden["small_sim_gl_sum"]         # the data the reference ran on
     em = orclib.OracleEM(orc_libm, gl, d.pos_dist_mb)
     em.set_params(0.3, 0.05, 0.2)
     em.init_emission()
@@ -66,9 +79,9 @@ def test_batched_bfgs_against_reference_object(pkg, orc_libm, ref_bfgs, small_si
     x0F = np.full(d.n_ind, 0.3)
     x0A = np.full(d.n_ind, 0.05)
     F, A, st = hm.bfgs_batch_host(x0F, x0A, lambda i, f, a: -orc_libm.lkl([f, a], e[i], pos))
+    x = ref_golden["batched_x"]
     for i in range(d.n_ind):
-        x, _ = _scalar_findmax(orc_libm, ref_bfgs.findmax, e[i], pos, [0.3, 0.05])
-        assert x[0] == F[i] and x[1] == A[i]
+        assert x[i, 0] == F[i] and x[i, 1] == A[i]
 
 
 @pytest.mark.parametrize("fixed", [(False, False), (True, False), (False, True)])

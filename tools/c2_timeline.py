@@ -2,7 +2,7 @@
 """One steady-state EM iteration out of a rocprofv3 kernel trace: every dispatch with its queue,
 its start relative to the iteration's first kernel, its duration and the gap to the previous
 dispatch's end on the same queue.  An iteration starts at a fresh walk (the emitting k_fast_lkl_fd); the one printed is the 13th of the
-trace -- inside the timed loop of `bench.py --steps 10 --warmup 6` (tools/c2_timeline.sh); the last ten of
+trace -- inside the timed loop of `bench.py --full --steps 10 --warmup 6` (tools/c2_timeline.sh); the last ten of
 that run are bench.py's own measuring loops (events on, then one stream), where kernels run one after the other.
   python tools/c2_timeline.py kernel_trace.csv [iteration]"""
 import csv

@@ -8,7 +8,7 @@ mkdir -p $OUT
 WLS=${@:-c3 c3r c3r2 c3hi c2 c2r c2k c5k}
 for w in $WLS; do
   echo "== $w" | tee -a $OUT/progress.log
-  timeout -k 10 400 python3 bench.py --workload $w --steps 10 --warmup 5 --no_cpu_baseline --no_exact_line \
+  timeout -k 10 400 python3 bench.py --workload $w --full --steps 10 --warmup 5 --no_cpu_baseline --no_exact_line \
       > $OUT/bench_$w.json 2> $OUT/bench_$w.err || { echo "bench $w failed: $?" | tee -a $OUT/progress.log; tail -5 $OUT/bench_$w.err; }
   python3 - <<PY | tee -a $OUT/progress.log
 import json
