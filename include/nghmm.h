@@ -259,6 +259,46 @@ int nghmm_format_posteriors(nghmm_t* h, uint64_t ind_begin, uint64_t n_ind, char
  * "%f" values, 9 * rows * cols bytes.  NGHMM_ERR_ARG if a value is outside [0, 1]. */
 int nghmm_format_fixed6(nghmm_t* h, const double* values, uint64_t rows, uint64_t cols, char* out);
 
+/* ---- IBD tracts ----
+ * What scripts/convert_ibd.pl --ibd_pos makes of the .ibd file (convert_ibd.pl:99-130: one BED
+ * line per maximal run of 1 in an individual's Viterbi path on one chromosome), called on the
+ * device from the state the run left there -- the decoded path and the posteriors that
+ * EM.cpp:338-353 prints -- without the file.
+ *
+ * A tract of individual i is a maximal run of consecutive sites [a, b] such that every site in
+ * it is in state IBD and no site in (a, b] starts a chromosome (distance +inf).  In state IBD:
+ *   NGHMM_TRACTS_VITERBI    path[i][s] == 1 of the last nghmm_viterbi / nghmm_chain_viterbi
+ *                           decode of the loaded data (NGHMM_ERR_ARG if there was none since the
+ *                           load); threshold is ignored
+ *   NGHMM_TRACTS_POSTERIOR  marg_prob[i][s][1] >= threshold, threshold in (0, 1] (else, NaN
+ *                           included, NGHMM_ERR_ARG): the value nghmm_get_posteriors returns
+ * post_sum = the sum of marg_prob[i][s][1] over the tract's sites (the posteriors of the last
+ * E-step, zeros before the first), added piece by piece in site order: the same bits on every
+ * call.  Tracts of fewer than min_sites sites are dropped; records are ordered by
+ * (ind, first_site). */
+enum { NGHMM_TRACTS_VITERBI = 0, NGHMM_TRACTS_POSTERIOR = 1 };
+typedef struct nghmm_tract {  /* 32 bytes */
+  uint64_t first_site;        /* handle-local (single handle) or global (chain) */
+  uint64_t n_sites;
+  uint32_t ind;
+  uint32_t reserved;          /* 0 */
+  double post_sum;
+} nghmm_tract;
+/* Tracts of one handle (convert_ibd.pl:99-130 on the path EM.cpp:338-353 prints): *n_total
+ * receives the number of tracts, out (host) the first min(cap, *n_total) of them; out may be
+ * NULL when cap == 0.  Device scratch grows with the number of tracts (NGHMM_ERR_NOMEM when it
+ * cannot be had). */
+int nghmm_ibd_tracts(nghmm_t* h, int source, double threshold, uint64_t min_sites,
+                     nghmm_tract* out, uint64_t cap, uint64_t* n_total);
+/* The same over a chain of site shards (nghmm_chain_setup; convert_ibd.pl:99-130,
+ * EM.cpp:338-353): global site indices; a tract that crosses a shard boundary is one tract
+ * unless the next shard's first site starts a chromosome; min_sites applies AFTER merging;
+ * post_sum = the sum of the pieces in site order.  (Chains of more than one handle are fast
+ * mode only, as nghmm_chain_setup requires.) */
+int nghmm_chain_ibd_tracts(nghmm_t** hs, int n, int source, double threshold,
+                           uint64_t min_sites, nghmm_tract* out, uint64_t cap,
+                           uint64_t* n_total);
+
 /* ---- multi-GPU (individuals sharded over ranks) ----
  * The allele-frequency step needs every individual of a site.  A rank owns the
  * individuals [ind_begin, ind_begin + n_ind) of n_ind_total for all sites, and

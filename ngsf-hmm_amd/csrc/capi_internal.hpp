@@ -90,6 +90,15 @@ struct nghmm_handle {
   char* d_text = nullptr;    // formatted posterior lines of one batch of individuals
   size_t text_cap = 0;
   bool tmp_is_posteriors = false;  // d_tmp holds the [I][S] posteriors of the last E-step
+  // d_path_sites holds a decoded path of the loaded data (nghmm_geno_posteriors allocates and
+  // zeroes it before any decode)
+  bool path_decoded = false;
+  // IBD tracts (capi_tracts.hip): per (individual, segment) counts / offsets, carried sums, the
+  // chromosome-start mask and scan scratch; the records (raw, then compacted) and their offsets
+  uint8_t* d_tseg = nullptr;
+  size_t tseg_cap = 0;
+  uint8_t* d_trec = nullptr;
+  size_t trec_cap = 0;
   uint32_t* d_passes = nullptr;
   double *d_freq_new = nullptr, *d_hap = nullptr;  // --freq_est 2 as intended: [S], [S][4]
 
@@ -202,6 +211,11 @@ int estmaf_and_refresh(nghmm_t* h, bool shard, const double* d_marg_blocks, uint
                        uint64_t I_tot, uint64_t I_blk, double* d_freq_out);
 // leaves its chain, which dissolves (capi_multi.hip)
 void chain_release(nghmm_t* h);
+// the IBD tracts of one handle (handle-local sites), all of them, to the host (capi_tracts.hip)
+int tracts_to_host(nghmm_t* h, int source, double threshold, uint64_t min_sites,
+                   std::vector<nghmm_tract>& out);
+// source / threshold of nghmm_ibd_tracts; sets the error message
+int tracts_check_args(nghmm_t* h, int source, double threshold, const char* who);
 
 template <typename T>
 int dev_alloc(T** p, size_t n) {

@@ -8,6 +8,7 @@ static int after_gl_load(nghmm_t* h) {
   h->loading = false;
   h->marg_valid = false;  // nothing derived from earlier data survives a (re)load
   h->tmp_is_posteriors = false;
+  h->path_decoded = false;
   if (h->packed) {
     // the value the data's uniform cells carry becomes row 3 of the class table
     unsigned long long bits = ~0ull;

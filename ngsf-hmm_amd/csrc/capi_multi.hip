@@ -121,6 +121,7 @@ int nghmm_viterbi_shard_back(nghmm_t* h, const uint8_t* state_after, uint8_t* st
   if (e == hipSuccess) e = sync_stream(h);
   (void)hipFree(d_before);
   HIP_TRY(e);
+  h->path_decoded = true;
   return NGHMM_OK;
 }
 
@@ -730,6 +731,68 @@ int nghmm_chain_viterbi(nghmm_t** hs, int n, uint8_t* path) {
     for (uint64_t i = 0; i < I; ++i) std::memcpy(path + i * S_tot + lo, part.data() + i * S, S);
     hi = lo;
   }
+  return NGHMM_OK;
+}
+
+// Tracts over a chain: every handle's tracts (min_sites 1) on its own device, then one pass on
+// the host in (individual, rank) order that joins a tract starting at a handle's first site to
+// the individual's tract ending at the handle before's last site -- unless that first site
+// starts a chromosome -- and applies min_sites to what is joined.
+int nghmm_chain_ibd_tracts(nghmm_t** hs, int n, int source, double threshold, uint64_t min_sites,
+                           nghmm_tract* out, uint64_t cap, uint64_t* n_total) {
+  g_last_error.clear();
+  if (!is_chain(hs, n)) {
+    set_error("nghmm_chain_ibd_tracts: call nghmm_chain_setup on these handles first");
+    return NGHMM_ERR_ARG;
+  }
+  if (n == 1) return nghmm_ibd_tracts(hs[0], source, threshold, min_sites, out, cap, n_total);
+  if (!n_total || (cap && !out)) {
+    set_error("nghmm_chain_ibd_tracts: n_total is NULL, or out is NULL with cap > 0");
+    return NGHMM_ERR_ARG;
+  }
+  int rc;
+  for (int r = 0; r < n; ++r)
+    if ((rc = tracts_check_args(hs[r], source, threshold, "nghmm_chain_ibd_tracts"))) return rc;
+  std::vector<std::vector<nghmm_tract>> parts(n);
+  std::vector<uint64_t> base(n);
+  std::vector<char> chrom_start(n);
+  uint64_t S_tot = 0;
+  for (int r = 0; r < n; ++r) {
+    nghmm_t* h = hs[r];
+    base[r] = S_tot;
+    S_tot += h->S;
+    if ((rc = tracts_to_host(h, source, threshold, 1, parts[r]))) return rc;
+    double d0 = 0;
+    HIP_TRY(hipMemcpyAsync(&d0, h->d_pos, sizeof d0, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(sync_stream(h));
+    chrom_start[r] = std::isinf(d0);
+  }
+  std::vector<nghmm_tract> all;
+  std::vector<size_t> at(n, 0);
+  for (uint64_t i = 0; i < hs[0]->I; ++i) {
+    const size_t ind_first = all.size();
+    for (int r = 0; r < n; ++r) {
+      const std::vector<nghmm_tract>& v = parts[r];
+      for (; at[r] < v.size() && v[at[r]].ind == i; ++at[r]) {
+        nghmm_tract t = v[at[r]];
+        t.first_site += base[r];
+        if (r > 0 && !chrom_start[r] && t.first_site == base[r] && all.size() > ind_first &&
+            all.back().first_site + all.back().n_sites == base[r]) {
+          all.back().n_sites += t.n_sites;
+          all.back().post_sum += t.post_sum;
+        } else {
+          all.push_back(t);
+        }
+      }
+    }
+  }
+  uint64_t kept = 0;
+  for (const nghmm_tract& t : all)
+    if (t.n_sites >= min_sites) {
+      if (kept < cap) out[kept] = t;
+      ++kept;
+    }
+  *n_total = kept;
   return NGHMM_OK;
 }
 

@@ -7,7 +7,9 @@
 // include/nghmm.h (HIP kernels).  Host-side work is what the reference also does once,
 // outside its hot loop: argument parsing, file I/O, GL normalisation, initial values.
 //
-// Extra options: --mode exact|fast (default fast), --device N.  --n_threads (the
+// Extra options: --mode exact|fast (default fast), --device N, --ibd_bed [--ind_names FILE]
+// (PREFIX.ibd.bed: the IBD tracts of the .ibd path lines as scripts/convert_ibd.pl --ibd_pos
+// prints them, called on the device).  --n_threads (the
 // reference's pool size) sets the host threads used for input normalisation and output
 // formatting; results do not depend on it.
 #include <fcntl.h>
@@ -34,6 +36,10 @@
 #include <vector>
 
 #include "../../../include/nghmm.h"
+
+// referenced weakly: a build against a library without the tract entry still links, and
+// --ibd_bed then stops with a message
+#pragma weak nghmm_chain_ibd_tracts
 
 namespace {
 
@@ -70,6 +76,15 @@ struct Params {  // ngsF-HMM.hpp:13-52
   FILE* out = stdout;            // where this run's progress lines go (replicates: a buffer)
   std::string prefix;            // output prefix of this run
   std::vector<double> pos_dist;  // [S] Mb
+  // --ibd_bed: PREFIX.ibd.bed next to every .ibd file (convert_ibd.pl --ibd_pos); --ind_names
+  // FILE: the individuals' IDs (first field of each line), default ind<i>
+  bool ibd_bed = false;
+  const char* in_ind_names = nullptr;
+  std::vector<std::string> ind_names;
+  std::vector<uint64_t> site_pos;           // [S] the .pos file's integer positions
+  std::vector<uint64_t> chrom_first;        // first site of every run of one chromosome name
+  std::vector<std::string> chrom_name;      // ... and that name
+  bool decoded = false;                     // path holds a Viterbi decode
   std::vector<double> freq, indF, alpha, ind_lkl;
   std::vector<uint8_t> path;
   double tot_lkl = 0, prev_tot_lkl = 0;
@@ -455,6 +470,9 @@ void read_dist(Params& P) {
   if (!fh) fatal(__FUNCTION__, "cannot open POS file!");
   std::vector<char> buf(kBuffLen);
   P.pos_dist.assign(P.n_sites, INFINITY);
+  P.site_pos.assign(P.n_sites, 0);
+  P.chrom_first.clear();
+  P.chrom_name.clear();
   std::string prev_chr;
   uint64_t prev_pos = 0, s = 0;
   while (gzgets(fh, buf.data(), (int)kBuffLen) != nullptr) {
@@ -477,7 +495,12 @@ void read_dist(Params& P) {
       P.pos_dist[s] = INFINITY;
       prev_chr = chr;
     }
+    if (s == 0 || std::isinf(P.pos_dist[s])) {
+      P.chrom_first.push_back(s);
+      P.chrom_name.push_back(chr);
+    }
     prev_pos = strtoul(pos_s, nullptr, 0);
+    P.site_pos[s] = prev_pos;
     s++;
   }
   gzclose(fh);
@@ -1060,6 +1083,8 @@ class PositionalWriter {
 };
 
 // EM.cpp:293-380
+void write_ibd_bed(const Params& P, Cohort& C);
+
 void print_iter(const Params& P, Cohort& C) {
   const double t_p0 = omp_get_wtime();
   const uint64_t I = P.n_ind, S = P.n_sites;
@@ -1200,7 +1225,50 @@ void print_iter(const Params& P, Cohort& C) {
             "buffer %.2f s, last writes %.2f s\n", t_w1 - t_w0, t_dev, t_host, t_wait, omp_get_wtime() - t_w2);
   const double t_c0 = omp_get_wtime();
   if (close(fd_geno) != 0 || close(fd_ibd) != 0) fatal(__FUNCTION__, "cannot write the output files!");
+  if (P.ibd_bed) write_ibd_bed(P, C);
   if (P.verbose >= 2) fprintf(P.out, "> output: close %.2f s, before the buffers %.2f s\n", omp_get_wtime() - t_c0, t_w0 - t_p0);
+}
+
+// PREFIX.ibd.bed: what scripts/convert_ibd.pl --ibd_pos PREFIX.ibd --pos POS --ind NAMES prints
+// (convert_ibd.pl:99-130) -- one line "CHR START END IND_ID LENGTH" per maximal run of 1 in an
+// individual's path line on one chromosome, START = pos[first] - 1, END = pos[last] -- from the
+// tracts called on the device (nghmm_chain_ibd_tracts, the Viterbi path, no minimum length).
+// Before the first decode the path lines are all 0: no line.
+void write_ibd_bed(const Params& P, Cohort& C) {
+  if (!nghmm_chain_ibd_tracts)
+    fatal(__FUNCTION__, "--ibd_bed: the library has no nghmm_chain_ibd_tracts!");
+  const uint64_t I = P.n_ind, S = P.n_sites;
+  std::vector<nghmm_tract> t;
+  if (P.decoded) {
+    uint64_t n = 0;
+    check(nghmm_chain_ibd_tracts(C.hs.data(), C.n(), NGHMM_TRACTS_VITERBI, 0.5, 1, nullptr, 0, &n),
+          "ibd_tracts");
+    t.resize(n);
+    uint64_t got = 0;
+    if (n) check(nghmm_chain_ibd_tracts(C.hs.data(), C.n(), NGHMM_TRACTS_VITERBI, 0.5, 1, t.data(), n, &got),
+                 "ibd_tracts");
+    if (got != n) fatal(__FUNCTION__, "the number of tracts changed between two calls!");
+  }
+  const std::string name = P.prefix + ".ibd.bed";
+  FILE* fh = fopen(name.c_str(), "w");
+  if (!fh) fatal(__FUNCTION__, "cannot open IBD BED output file!");
+  setvbuf(fh, nullptr, _IOFBF, 1 << 22);
+  size_t c = 0;  // the chromosome run of the tract's first site (records come in site order per individual)
+  uint32_t prev_ind = UINT32_MAX;
+  for (const nghmm_tract& r : t) {
+    if (r.ind >= I || r.n_sites == 0 || r.first_site >= S || r.n_sites > S - r.first_site)
+      fatal(__FUNCTION__, "a tract outside the data!");
+    const std::string id = P.ind_names.empty() ? "ind" + std::to_string(r.ind) : P.ind_names[r.ind];
+    // the script skips individuals whose ID Perl reads as false ("" or "0")
+    if (id.empty() || id == "0") continue;
+    if (r.ind != prev_ind || P.chrom_first[c] > r.first_site) c = 0;
+    prev_ind = r.ind;
+    while (c + 1 < P.chrom_first.size() && P.chrom_first[c + 1] <= r.first_site) c++;
+    const uint64_t start = P.site_pos[r.first_site] - 1, end = P.site_pos[r.first_site + r.n_sites - 1];
+    fprintf(fh, "%s\t%llu\t%llu\t%s\t%lld\n", P.chrom_name[c].c_str(), (unsigned long long)start,
+            (unsigned long long)end, id.c_str(), (long long)(end - start));
+  }
+  if (fclose(fh) != 0) fatal(__FUNCTION__, "cannot write the IBD BED output file!");
 }
 
 void sync_outputs(Params& P, Cohort& C, bool with_viterbi) {
@@ -1210,7 +1278,10 @@ void sync_outputs(Params& P, Cohort& C, bool with_viterbi) {
     check(nghmm_get_params(C.hs[r], r == 0 ? P.indF.data() : nullptr, r == 0 ? P.alpha.data() : nullptr,
                            P.freq.data() + C.lo[r]),
           "print_iter");
-  if (with_viterbi) check(nghmm_chain_viterbi(C.hs.data(), C.n(), P.path.data()), "viterbi");
+  if (with_viterbi) {
+    check(nghmm_chain_viterbi(C.hs.data(), C.n(), P.path.data()), "viterbi");
+    P.decoded = true;
+  }
 }
 
 void parse_cmd_args(Params& P, int argc, char** argv) {  // parse_args.cpp:41-225
@@ -1232,6 +1303,7 @@ void parse_cmd_args(Params& P, int argc, char** argv) {  // parse_args.cpp:41-22
       {"keep_starts", no_argument, nullptr, 1005},    {"n_gpus", required_argument, nullptr, 1006},
       {"devices", required_argument, nullptr, 1007},  {"ld_intended", no_argument, nullptr, 1008},
       {"parse_kat", no_argument, nullptr, 1009},
+      {"ibd_bed", no_argument, nullptr, 1010},        {"ind_names", required_argument, nullptr, 1011},
       {0, 0, 0, 0}};
   long taus_kat = 0;
   bool parse_kat = false;
@@ -1264,6 +1336,8 @@ void parse_cmd_args(Params& P, int argc, char** argv) {  // parse_args.cpp:41-22
       case 'S': P.seed = atoi(optarg); break;
       case 1008: P.ld_intended = true; break;
       case 1009: parse_kat = true; break;
+      case 1010: P.ibd_bed = true; break;
+      case 1011: P.in_ind_names = optarg; break;
       case 1000:
         if (!strcmp(optarg, "exact")) P.mode = NGHMM_MODE_EXACT;
         else if (!strcmp(optarg, "fast")) P.mode = NGHMM_MODE_FAST;
@@ -1352,6 +1426,24 @@ void parse_cmd_args(Params& P, int argc, char** argv) {  // parse_args.cpp:41-22
       fatal(__FUNCTION__, "too few sites for --n_gpus (the site axis is what the GPUs share)!");
     if (P.mode != NGHMM_MODE_FAST) fatal(__FUNCTION__, "--n_gpus > 1 needs --mode fast!");
     if (P.n_starts > 1) fatal(__FUNCTION__, "--n_starts and --n_gpus > 1 cannot be combined!");
+  }
+  if (P.in_ind_names) {  // the first tab- or space-separated field of each line (convert_ibd.pl --ind)
+    gzFile fh = gzopen(P.in_ind_names, "r");
+    if (!fh) fatal(__FUNCTION__, "cannot open individual names file (--ind_names)!");
+    std::vector<char> buf(kBuffLen);
+    while (gzgets(fh, buf.data(), (int)kBuffLen) != nullptr) {
+      chomp(buf.data());
+      const std::string id(buf.data(), strcspn(buf.data(), "\t "));
+      if (id.empty()) {
+        gzclose(fh);
+        fatal(__FUNCTION__, "empty individual name in --ind_names file!");
+      }
+      P.ind_names.push_back(id);
+    }
+    gzclose(fh);
+    if (P.ind_names.size() != P.n_ind)
+      fatal(__FUNCTION__, "number of lines in --ind_names file is not --n_ind!");
+    if (!P.ibd_bed) warn(__FUNCTION__, "--ind_names is only used by --ibd_bed");
   }
   P.prefix = P.out_prefix;
 }
@@ -1564,7 +1656,8 @@ int main(int argc, char** argv) {
       free(bufs[r]);
     }
     if (P.keep_starts) {  // the script moves the best replicate's files to the output prefix
-      for (const char* ext : {".indF", ".ibd", ".geno"}) {
+      for (const char* ext : {".indF", ".ibd", ".geno", ".ibd.bed"}) {
+        if (!P.ibd_bed && !strcmp(ext, ".ibd.bed")) continue;
         const std::string from = runs[best].prefix + ext, to = std::string(P.out_prefix) + ext;
         FILE* a = fopen(from.c_str(), "rb");
         FILE* b = fopen(to.c_str(), "wb");

@@ -133,4 +133,38 @@ void launch_format_fixed6(hipStream_t st, const double* in, uint64_t rows, uint6
 // out[(s - lo) * I + i] = marg[s][i] for s in [lo, hi): a contiguous slice copy in site-major
 void launch_copy_f64(hipStream_t st, const double* in, double* out, uint64_t n);
 
+// ---------------- IBD tracts (kernels_tracts.hip) ----------------
+// One record per tract, laid out as nghmm_tract (include/nghmm.h).  Between the emit and the
+// finish pass n_sites holds the tract's last site and post_sum its first piece's sum.
+struct TractRec {
+  uint64_t first_site, n_sites;
+  uint32_t ind, reserved;
+  double post_sum;
+};
+static_assert(sizeof(TractRec) == 32, "nghmm_tract is 32 bytes");
+enum { TRACTS_SRC_VITERBI = 0, TRACTS_SRC_POSTERIOR = 1 };   // = NGHMM_TRACTS_*
+constexpr uint64_t kTractSeg = 2048;   // sites per lane of the count and emit passes (x16)
+uint64_t tract_segments(uint64_t S);
+// mask[(S+15)/16]: bit u of word b = site 16 b + u is site 0 or has distance +inf
+void launch_tract_chrom_mask(hipStream_t st, const double* pos, uint64_t S, uint32_t* mask);
+// in state: path16[blocked] != 0 (VITERBI) or marg[s][i] >= thr (POSTERIOR);
+// counts[I][tract_segments(S)] = tracts starting in each segment
+void launch_tract_count(hipStream_t st, int src, const uint8_t* path16, const double* marg,
+                        double thr, const uint32_t* cmask, uint64_t S, uint64_t I,
+                        uint64_t* counts);
+// off = the exclusive scan of counts; rec[off total]; carry[I][tract_segments(S)]
+void launch_tract_emit(hipStream_t st, int src, const uint8_t* path16, const double* marg,
+                       double thr, const uint32_t* cmask, uint64_t S, uint64_t I,
+                       const uint64_t* off, TractRec* rec, double* carry);
+// final n_sites and post_sum in place; keep[n] (may be NULL) = n_sites >= min_sites
+void launch_tract_finish(hipStream_t st, TractRec* rec, uint64_t n, const double* carry,
+                         uint64_t S, uint64_t min_sites, uint64_t* keep);
+// out[off[k]] = rec[k] for the records with n_sites >= min_sites (off = scan of keep)
+void launch_tract_compact(hipStream_t st, const TractRec* rec, uint64_t n, uint64_t min_sites,
+                          const uint64_t* off, TractRec* out);
+// exclusive scan of d[n] in place, d[n] = the total (d has n + 1 elements);
+// scratch[tract_scan_scratch(n)]
+uint64_t tract_scan_scratch(uint64_t n);
+void launch_tract_scan(hipStream_t st, uint64_t* d, uint64_t n, uint64_t* scratch);
+
 }  // namespace nghmm

@@ -141,6 +141,8 @@ def load_library():
         "nghmm_viterbi_shard_forward": (i32, [vp, dp, dp]),
         "nghmm_viterbi_shard_back": (i32, [vp, C.POINTER(C.c_uint8), C.POINTER(C.c_uint8),
                                            C.POINTER(C.c_uint8)]),
+        "nghmm_ibd_tracts": (i32, [vp, i32, d, u64, vp, u64, C.POINTER(u64)]),
+        "nghmm_chain_ibd_tracts": (i32, [C.POINTER(vp), i32, i32, d, u64, vp, u64, C.POINTER(u64)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -176,6 +178,7 @@ EXPORTED_SYMBOLS = [
     "nghmm_site_shard_bytes", "nghmm_site_shard_setup", "nghmm_viterbi_shard_forward",
     "nghmm_viterbi_shard_back", "nghmm_chain_setup", "nghmm_chain_iter_em", "nghmm_chain_mstep_freq",
     "nghmm_chain_viterbi", "nghmm_alloc_host", "nghmm_free_host",
+    "nghmm_ibd_tracts", "nghmm_chain_ibd_tracts",
 ]
 
 OBJECTIVE_FN = C.CFUNCTYPE(C.c_double, C.c_uint32, C.c_double, C.c_double, C.c_void_p)
@@ -203,6 +206,61 @@ def bfgs_batch_host(indF, alpha, objective, indF_fixed=False, alpha_fixed=False,
     if rc != 0:
         raise NgsFHMMError(rc, L.nghmm_strerror(rc).decode())
     return F, A, st
+
+
+TRACTS_VITERBI = 0    # nghmm_ibd_tracts sources (include/nghmm.h)
+TRACTS_POSTERIOR = 1
+
+
+class Tract(C.Structure):            # nghmm_tract (include/nghmm.h)
+    _fields_ = [("first_site", C.c_uint64), ("n_sites", C.c_uint64), ("ind", C.c_uint32),
+                ("reserved", C.c_uint32), ("post_sum", C.c_double)]
+
+
+TRACT_DTYPE = np.dtype([("ind", np.uint32), ("first_site", np.uint64), ("n_sites", np.uint64),
+                        ("post_sum", np.float64), ("post_mean", np.float64)])
+
+
+def _tract_source(source):
+    src = {"viterbi": TRACTS_VITERBI, "posterior": TRACTS_POSTERIOR}.get(source, source)
+    if src not in (TRACTS_VITERBI, TRACTS_POSTERIOR):
+        raise NgsFHMMError(-10, f"ibd_tracts: unknown source {source!r} ('viterbi' or 'posterior')")
+    return src
+
+
+def _tracts(call, check, source, threshold, min_sites):
+    """One call for the count, one to fetch (nghmm_ibd_tracts / nghmm_chain_ibd_tracts)."""
+    src = _tract_source(source)
+    n = C.c_uint64(0)
+    check(call(src, float(threshold), int(min_sites), None, 0, C.byref(n)))
+    buf = (Tract * max(n.value, 1))()
+    if n.value:
+        got = C.c_uint64(0)
+        check(call(src, float(threshold), int(min_sites), C.cast(buf, C.c_void_p), n.value,
+                   C.byref(got)))
+        assert got.value == n.value
+    raw = np.frombuffer(buf, dtype=np.dtype([("first_site", np.uint64), ("n_sites", np.uint64),
+                                             ("ind", np.uint32), ("reserved", np.uint32),
+                                             ("post_sum", np.float64)]), count=n.value)
+    out = np.empty(n.value, dtype=TRACT_DTYPE)
+    for f in ("ind", "first_site", "n_sites", "post_sum"):
+        out[f] = raw[f]
+    out["post_mean"] = out["post_sum"] / np.maximum(out["n_sites"], 1)
+    return out
+
+
+def bed_lines(tracts, chrom_names, positions, ind_names):
+    """BED text of tract records as scripts/convert_ibd.pl --ibd_pos prints it
+    (convert_ibd.pl:99-130): ``CHR  START  END  IND_ID  LENGTH`` tab-separated, one line per
+    tract, with START = pos[first] - 1, END = pos[last], LENGTH = END - START.
+    chrom_names / positions: per site (global site index); ind_names: per individual."""
+    lines = []
+    for t in tracts:
+        a = int(t["first_site"])
+        b = a + int(t["n_sites"]) - 1
+        start, end = int(positions[a]) - 1, int(positions[b])
+        lines.append(f"{chrom_names[a]}\t{start}\t{end}\t{ind_names[int(t['ind'])]}\t{end - start}\n")
+    return "".join(lines)
 
 
 KERNEL_SLOTS = {"emission": 0, "forward": 1, "backward": 2, "lkl_batch": 3, "est_maf": 4,
@@ -568,6 +626,14 @@ class NgsFHMM:
         self._check(self.lib.nghmm_viterbi(self._h, path.ctypes.data_as(C.POINTER(C.c_uint8))))
         return path
 
+    def ibd_tracts(self, source="viterbi", threshold=0.5, min_sites=1):
+        """IBD tracts called on the device (nghmm_ibd_tracts): maximal runs of the IBD state
+        within one chromosome, from the last Viterbi decode ("viterbi") or from posteriors
+        >= threshold ("posterior").  Structured array with fields ind, first_site, n_sites,
+        post_sum, post_mean, ordered by (ind, first_site)."""
+        return _tracts(lambda *a: self.lib.nghmm_ibd_tracts(self._h, *a), self._check, source,
+                       threshold, min_sites)
+
     # -- measurement -------------------------------------------------------
     def kernel_ms(self, name):
         """(milliseconds, launches) of a kernel family in the last call that ran it.  Fast mode's
@@ -678,6 +744,13 @@ class Chain:
         self.handles[0]._check(self.lib.nghmm_chain_viterbi(
             self._arr, len(self.handles), path.ctypes.data_as(C.POINTER(C.c_uint8))))
         return path
+
+    def ibd_tracts(self, source="viterbi", threshold=0.5, min_sites=1):
+        """NgsFHMM.ibd_tracts over the chain (nghmm_chain_ibd_tracts): global site indices, a
+        tract across a shard boundary joined into one, min_sites applied after joining."""
+        self._members_open()
+        return _tracts(lambda *a: self.lib.nghmm_chain_ibd_tracts(self._arr, len(self.handles), *a),
+                       self.handles[0]._check, source, threshold, min_sites)
 
     @property
     def freq(self):
