@@ -7,6 +7,10 @@
 
 #include <mutex>
 
+namespace capi {
+void set_error(const char* fmt, ...);  // the message of the failing call (capi_internal.hpp)
+}
+
 namespace nghmm {
 
 namespace {
@@ -1189,7 +1193,9 @@ __device__ void estmaf_stream_site(const GlView& gl, const double* __restrict__ 
                             : marg_blocks[((i / I_blk) * S_own + site) * I_blk + (i % I_blk)];
       const double bF = b * F;
       const double h0 = A + bF, h2 = Cq + bF;
-      const double h1 = (F == 1) ? 0.0 : (2 * b - 2 * bF);
+      // 2 b (1 - F): 1 - F is exact next to 1, where the reference's 2 b - 2 b F cancels (as in
+      // the register kernels' 2 p1 (1 - F))
+      const double h1 = (F == 1) ? 0.0 : (2 * b) * (1 - F);
       double p0, p1, p2;
       gl_fetch(gl, cell_s + i, p0, p1, p2);
       const double w0 = p0 * h0, w1 = p1 * h1, w2 = p2 * h2;
@@ -1201,11 +1207,11 @@ __device__ void estmaf_stream_site(const GlView& gl, const double* __restrict__ 
         pd += fma(w0 + w2, tF, 2 * w1) * inv;
       } else {
         // a called genotype's impossible classes are -1e15 in the reference (read_data.cpp:21),
-        // not -inf: the packed view knows it holds such cells
+        // not -inf, in a packed view and in dense one-hot likelihoods alike: a linear 0 is that
+        // stand-in (the reference has no -inf: every log 0 it reads becomes -1e15)
         double lg[3] = {log(p0), log(p1), log(p2)};
-        if (!gl.dense)
-          for (int k = 0; k < 3; ++k)
-            if (lg[k] == -__builtin_huge_val()) lg[k] = -kINF;
+        for (int k = 0; k < 3; ++k)
+          if (lg[k] == -__builtin_huge_val()) lg[k] = -kINF;
         const double2 tt = estmaf_term_logspace(lg, freq, F);
         pn += tt.x;
         pd += tt.y;
@@ -1292,24 +1298,29 @@ bool fast_estmaf_reserve(FastState& fs, uint64_t S_own) {
   return true;
 }
 
-// dynamic LDS of an est_maf kernel; beyond 64 KB the kernel has to be told once
-static size_t estmaf_dyn_lds(const void* kernel, size_t bytes) {
-  if (bytes > 65536) {
-    // (per device: the handles of a chain sit on several; under a lock: replicas launch from
-    // several host threads)
-    static std::vector<std::pair<const void*, int>> told;
-    static std::mutex mu;
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    std::lock_guard<std::mutex> lock(mu);
-    const std::pair<const void*, int> key{kernel, dev};
-    if (std::find(told.begin(), told.end(), key) == told.end()) {
-      if (hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess)
-        (void)hipGetLastError();
-      told.push_back(key);
-    }
+// dynamic LDS of an est_maf kernel; beyond 64 KB the kernel has to be told once.  False (with
+// the message of the failing call set) when the runtime refuses: the kernel is not launched.
+static bool estmaf_dyn_lds(const void* kernel, size_t bytes) {
+  if (bytes <= 65536) return true;
+  // (per device: the handles of a chain sit on several; under a lock: replicas launch from
+  // several host threads)
+  static std::vector<std::pair<const void*, int>> told;
+  static std::mutex mu;
+  int dev = 0;
+  (void)hipGetDevice(&dev);
+  std::lock_guard<std::mutex> lock(mu);
+  const std::pair<const void*, int> key{kernel, dev};
+  if (std::find(told.begin(), told.end(), key) != told.end()) return true;
+  const hipError_t e =
+      hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    capi::set_error("est_maf: the kernel needs %zu bytes of dynamic LDS per workgroup and the "
+                    "device refuses them (hipFuncSetAttribute: %s)", bytes, hipGetErrorString(e));
+    return false;
   }
-  return bytes;
+  told.push_back(key);
+  return true;
 }
 
 bool fast_estmaf(FastState& fs, hipStream_t st, const GlView& d_gl_sites,
@@ -1365,37 +1376,40 @@ bool fast_estmaf(FastState& fs, hipStream_t st, const GlView& d_gl_sites,
   const unsigned scan_wgs = (unsigned)(scan_wgs_all < 16384 ? scan_wgs_all : 16384);
   // (kernels of several waves per site park the interval's partial node sums in dynamic LDS,
   // EN * B double2: 24 / 48 / 96 KB at 2 / 4 / 8 waves -- four, two, one workgroup per CU either way)
-#define ESTMAF_DYN(K, B)                                                                        \
-  ((B) > 64 ? estmaf_dyn_lds(reinterpret_cast<const void*>(K), (size_t)EN * (B) * sizeof(double2)) : (size_t)0)
+#define ESTMAF_DYN(B) ((B) > 64 ? (size_t)EN * (B) * sizeof(double2) : (size_t)0)
+#define ESTMAF_TELL(K, B) estmaf_dyn_lds(reinterpret_cast<const void*>(K), ESTMAF_DYN(B))
 #define LAUNCH_NI(N, B)                                                                         \
   do {                                                                                          \
-    if (fresh)                                                                                  \
-      hipLaunchKernelGGL((k_fast_estmaf<N, B, false>), dim3((unsigned)S_own), dim3(B),           \
-                         ESTMAF_DYN((k_fast_estmaf<N, B, false>), B), st,                        \
-                         d_gl_sites, d_marg_blocks, S_own, I_tot, I_blk, (uint64_t)0,           \
-                         d_freq_out, fs.redo, fs.est_status, fs.est_state, fs.redo_cap,         \
-                         n_exact, allow_build, (uint64_t)0, fs.est_counts);                     \
-    else                                                                                        \
+    if (fresh) {                                                                                \
+      if (!ESTMAF_TELL((k_fast_estmaf<N, B, false>), B)) return false;                          \
+      hipLaunchKernelGGL((k_fast_estmaf<N, B, false>), dim3((unsigned)S_own), dim3(B),          \
+                         ESTMAF_DYN(B), st, d_gl_sites, d_marg_blocks, S_own, I_tot, I_blk,     \
+                         (uint64_t)0, d_freq_out, fs.redo, fs.est_status, fs.est_state,         \
+                         fs.redo_cap, n_exact, allow_build, (uint64_t)0, fs.est_counts);        \
+    } else {                                                                                    \
+      if (!ESTMAF_TELL((k_fast_estmaf_resume<N, B, false>), B)) return false;                   \
       hipLaunchKernelGGL((k_fast_estmaf_resume<N, B, false>), dim3(scan_wgs), dim3(B),          \
-                         ESTMAF_DYN((k_fast_estmaf_resume<N, B, false>), B), st,                 \
-                         d_gl_sites, d_marg_blocks, S_own, I_tot, I_blk, (uint64_t)0,           \
-                         d_freq_out, fs.redo, fs.est_status, fs.est_state, fs.redo_cap,         \
-                         n_exact, allow_build, row0, row1, fs.est_counts, cnt_slot);            \
+                         ESTMAF_DYN(B), st, d_gl_sites, d_marg_blocks, S_own, I_tot, I_blk,     \
+                         (uint64_t)0, d_freq_out, fs.redo, fs.est_status, fs.est_state,         \
+                         fs.redo_cap, n_exact, allow_build, row0, row1, fs.est_counts,          \
+                         cnt_slot);                                                             \
+    }                                                                                           \
   } while (0)
 #define LAUNCH_TILE(N, B)                                                                       \
   do {                                                                                          \
-    if (fresh)                                                                                  \
+    if (fresh) {                                                                                \
+      if (!ESTMAF_TELL((k_fast_estmaf<N, B, true>), B)) return false;                           \
       hipLaunchKernelGGL((k_fast_estmaf<N, B, true>), dim3((unsigned)nblk), dim3(B),            \
-                         ESTMAF_DYN((k_fast_estmaf<N, B, true>), B), st,                         \
-                         d_gl_sites, d_marg_blocks, S_own, I_tot, I_blk, tile_T, d_freq_out,    \
-                         fs.redo, fs.est_status, fs.est_state, fs.redo_cap, n_exact,            \
-                         allow_build, blk0, fs.est_counts);                                     \
-    else                                                                                        \
+                         ESTMAF_DYN(B), st, d_gl_sites, d_marg_blocks, S_own, I_tot, I_blk,     \
+                         tile_T, d_freq_out, fs.redo, fs.est_status, fs.est_state, fs.redo_cap, \
+                         n_exact, allow_build, blk0, fs.est_counts);                            \
+    } else {                                                                                    \
+      if (!ESTMAF_TELL((k_fast_estmaf_resume<N, B, true>), B)) return false;                    \
       hipLaunchKernelGGL((k_fast_estmaf_resume<N, B, true>), dim3(scan_wgs), dim3(B),           \
-                         ESTMAF_DYN((k_fast_estmaf_resume<N, B, true>), B), st,                  \
-                         d_gl_sites, d_marg_blocks, S_own, I_tot, I_blk, tile_T, d_freq_out,    \
-                         fs.redo, fs.est_status, fs.est_state, fs.redo_cap, n_exact,            \
-                         allow_build, row0, row1, fs.est_counts, cnt_slot);                     \
+                         ESTMAF_DYN(B), st, d_gl_sites, d_marg_blocks, S_own, I_tot, I_blk,     \
+                         tile_T, d_freq_out, fs.redo, fs.est_status, fs.est_state, fs.redo_cap, \
+                         n_exact, allow_build, row0, row1, fs.est_counts, cnt_slot);            \
+    }                                                                                           \
   } while (0)
 #define LAUNCH_ROWS(N, TL)                                                                      \
   do {                                                                                          \
@@ -1487,6 +1501,7 @@ bool fast_estmaf(FastState& fs, hipStream_t st, const GlView& d_gl_sites,
                      I_tot, I_blk, tile_T, d_freq_out, redo, row0, row1, fs.est_counts);
 #undef LAUNCH_NI
 #undef ESTMAF_DYN
+#undef ESTMAF_TELL
 #undef LAUNCH_TILE
 #undef LAUNCH_ROWS
   return hipGetLastError() == hipSuccess;

@@ -169,7 +169,8 @@ double orc_calc_emission(const double gl[3], double maf, int k, int* bad) {
 }
 
 /* shared/gen_func.cpp:974-1009 (ignore_miss_data = false, indF != NULL) */
-double orc_est_maf(uint64_t n_ind, const double* gl_site, const double* indF, int* n_passes) {
+static double est_maf_passes(uint64_t n_ind, const double* gl_site, const double* indF,
+                             int* n_passes, double* deltas) {
   int iters = 0;
   int passes = 0;
   double num = 0;
@@ -188,9 +189,22 @@ double orc_est_maf(uint64_t n_ind, const double* gl_site, const double* indF, in
       den += 2 * pp[1] + (pp[0] + pp[2]) * (2 - F);
     }
     freq = num / den;
+    if (deltas) deltas[passes - 1] = ORC_ABS(prev_freq - freq);
   } while (ORC_ABS(prev_freq - freq) > ORC_EPSILON && iters++ < 100);
   if (n_passes) *n_passes = passes;
   return freq;
+}
+
+double orc_est_maf(uint64_t n_ind, const double* gl_site, const double* indF, int* n_passes) {
+  return est_maf_passes(n_ind, gl_site, indF, n_passes, NULL);
+}
+
+/* The same loop, and the |prev_freq - freq| every pass compared with EPSILON: deltas[0 ..
+ * *n_passes - 1], room for ORC_EST_MAF_MAX_PASSES.  For tests that have to know how close a
+ * site's stopping decision was. */
+double orc_est_maf_trace(uint64_t n_ind, const double* gl_site, const double* indF, int* n_passes,
+                         double* deltas) {
+  return est_maf_passes(n_ind, gl_site, indF, n_passes, deltas);
 }
 
 /* ------------------------------------------------------------------ */

@@ -69,6 +69,11 @@ double orc_calc_emission(const double gl[3], double maf, int k, int* bad);
  * indF = per-individual IBD posterior at that site. n_passes (optional) gets
  * the number of passes over the individuals. */
 double orc_est_maf(uint64_t n_ind, const double* gl_site, const double* indF, int* n_passes);
+/* the same loop; deltas[0 .. *n_passes - 1] (room for ORC_EST_MAF_MAX_PASSES) get the
+ * |prev_freq - freq| that every pass compared with EPSILON */
+#define ORC_EST_MAF_MAX_PASSES 102
+double orc_est_maf_trace(uint64_t n_ind, const double* gl_site, const double* indF, int* n_passes,
+                         double* deltas);
 
 /* ---- --freq_est 2 / --e_prob 2 as INTENDED (opt-in; parity unpinned: the reference aborts) ----
  * shared/gen_func.cpp:1076-1119: one normal-space EM iteration of the haplotype frequencies

@@ -57,6 +57,7 @@ class Oracle:
             "orc_check_interv": (d, [d, ip]),
             "orc_calc_emission": (d, [dp, d, i32, ip]),
             "orc_est_maf": (d, [u64, dp, dp, ip]),
+            "orc_est_maf_trace": (d, [u64, dp, dp, ip, dp]),
             "orc_forward": (i32, [dp, dp, d, dp, dp, u64, dp]),
             "orc_backward": (i32, [dp, dp, d, dp, dp, u64, dp]),
             "orc_viterbi": (d, [dp, d, dp, dp, u64, C.c_char_p]),
@@ -127,6 +128,15 @@ class Oracle:
         n = C.c_int(0)
         f = self.lib.orc_est_maf(len(indF), _dp(gl_site), _dp(indF), C.byref(n))
         return f, n.value
+
+    def est_maf_trace(self, gl_site, indF):
+        """est_maf plus the |delta freq| of every pass: (freq, passes, deltas[passes])."""
+        gl_site = np.ascontiguousarray(gl_site, dtype=np.float64)
+        indF = np.ascontiguousarray(indF, dtype=np.float64)
+        n = C.c_int(0)
+        deltas = np.zeros(102)
+        f = self.lib.orc_est_maf_trace(len(indF), _dp(gl_site), _dp(indF), C.byref(n), _dp(deltas))
+        return f, n.value, deltas[:n.value]
 
     # --freq_est 2 / --e_prob 2 as intended (parity unpinned: the reference aborts)
     def haplo_freq(self, p1, p2, maf1, maf2):
