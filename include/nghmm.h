@@ -299,6 +299,52 @@ int nghmm_chain_ibd_tracts(nghmm_t** hs, int n, int source, double threshold,
                            uint64_t min_sites, nghmm_tract* out, uint64_t cap,
                            uint64_t* n_total);
 
+/* ---- IBD paths sampled from the joint posterior ----
+ * Whole paths z drawn from P(z | data, theta) by forward filtering and backward sampling, with
+ * the handle's CURRENT parameters and emissions (as nghmm_viterbi uses them, not the last
+ * E-step's): what neither the Viterbi path (one path) nor the per-site posteriors (marginals of
+ * strongly dependent neighbours) give -- the distribution of anything that spans more than one
+ * site: the number of tracts, the longest one, the share of the genome that is IBD.  (The
+ * reference has no such function; the forward vector is that of shared/HMM.cpp:6-28.)
+ *
+ * Definition.  For individual i let a_s(k) ~ P(z_s = k, y_1..s) be the forward vector at site s,
+ * c_s = exp(-alpha_i d_s) (0 where d_s = +inf: a chromosome start), q = (1 - F_i, F_i) and
+ * T_s(k, l) = (1 - c_s) q_l + [k = l] c_s.  A draw is
+ *     z_{S-1}:  1 if u_{S-1} (a(0) + a(1)) < a(1)                       (a = a_{S-1})
+ *     z_s    :  1 if u_s (n0 + n1) < n1,  n_k = a_s(k) T_{s+1}(k, z_{s+1}),   s = S-2 ... 0
+ * (compared by multiplication; at a chromosome start T does not depend on k and z_s is drawn from
+ * a_s alone).  u is a function of (seed, draw, individual, GLOBAL site) only: Philox4x32-10
+ * (csrc/philox.h) with key = (seed low 32, seed high 32), counter = (p low 32, p high 32,
+ * individual, draw), p = global site >> 1; an even site takes the output words (x0, x1), an odd
+ * one (x2, x3); u = (((uint64)x_hi << 32 | x_lo) >> 11) 2^-53, x_lo the first word of the pair.
+ * Nothing else enters: not the launch geometry, not n_draws or n_keep, not the sharding.  (The
+ * forward vectors carry the mode's rounding -- fast mode within 1e-9 of exact mode -- so two modes
+ * or layouts can differ at a site whose u lies that close to its threshold, and from there on.)
+ *
+ * Per (draw, individual) the device reduces the path to a record, so that many draws never need
+ * their paths stored; ibd_mb adds the distances d_s of the sites s that continue a tract, per
+ * lane-chunk of the layout and then chunk by chunk in site order -- no atomics: the same bits on
+ * every call. */
+typedef struct nghmm_path_stats {  /* 32 bytes */
+  uint64_t ibd_sites;      /* sites in state 1 */
+  uint64_t n_tracts;       /* maximal runs of 1 within a chromosome (nghmm_ibd_tracts' definition) */
+  uint64_t longest_sites;  /* sites of the longest such run, 0 if none */
+  double ibd_mb;           /* sum over tracts of the distance from first to last site, in Mb */
+} nghmm_path_stats;
+/* n_draws paths per individual, draw d from (seed, d): stats [n_draws][I] (host, may be NULL);
+ * the first n_keep <= n_draws draws are returned as paths [n_keep][I][S] bytes 0/1 (host; NULL iff
+ * n_keep == 0).  NGHMM_ERR_ARG for a handle without data, n_draws == 0, n_keep > n_draws, a NULL
+ * mismatch.  Leaves the handle's Viterbi path, posteriors and parameters alone. */
+int nghmm_sample_paths(nghmm_t* h, uint64_t seed, uint32_t n_draws, nghmm_path_stats* stats,
+                       uint32_t n_keep, uint8_t* paths);
+/* The same over a chain of site shards (nghmm_chain_setup; the forward vector of
+ * shared/HMM.cpp:6-28 continued from shard to shard): paths [n_keep][I][all sites], global site
+ * indices in the generator; the forward vectors travel left to right and the sampled states right
+ * to left, as in nghmm_viterbi_shard_forward / _back; tracts and ibd_mb that cross a shard
+ * boundary are merged as nghmm_chain_ibd_tracts merges them. */
+int nghmm_chain_sample_paths(nghmm_t** hs, int n, uint64_t seed, uint32_t n_draws,
+                             nghmm_path_stats* stats, uint32_t n_keep, uint8_t* paths);
+
 /* ---- multi-GPU (individuals sharded over ranks) ----
  * The allele-frequency step needs every individual of a site.  A rank owns the
  * individuals [ind_begin, ind_begin + n_ind) of n_ind_total for all sites, and

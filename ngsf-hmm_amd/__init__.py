@@ -16,8 +16,10 @@ an :class:`NgsFHMM` raises.
 """
 from .hmm import (NgsFHMM, NgsFHMMError, Group, Chain, MODE_EXACT, MODE_FAST, GENO_PACKED, LD_INTENDED, EPROB_LD, library_path,
                   load_library,
-                  build_library, bed_lines, TRACTS_VITERBI, TRACTS_POSTERIOR)
+                  build_library, bed_lines, TRACTS_VITERBI, TRACTS_POSTERIOR, PATH_STATS_DTYPE,
+                  path_stats_summary)
 from . import simulate
 
 __all__ = ["NgsFHMM", "NgsFHMMError", "Group", "Chain", "MODE_EXACT", "MODE_FAST", "GENO_PACKED", "LD_INTENDED", "EPROB_LD", "library_path",
-           "load_library", "build_library", "simulate", "bed_lines", "TRACTS_VITERBI", "TRACTS_POSTERIOR"]
+           "load_library", "build_library", "simulate", "bed_lines", "TRACTS_VITERBI", "TRACTS_POSTERIOR",
+           "PATH_STATS_DTYPE", "path_stats_summary"]

@@ -1,7 +1,7 @@
 // capi_internal.hpp -- what the translation units of the C ABI share: the handle, error plumbing,
 // and the helpers every entry point uses.  nghmm_capi.hip (handle life cycle, single-handle EM),
-// capi_load.hip (loaders), capi_output.hip (read-back and output formatting) and capi_multi.hip
-// (individual shards, site shards, groups and chains of handles) implement include/nghmm.h.
+// capi_load.hip (loaders), capi_output.hip (read-back and output formatting), capi_tracts.hip, capi_sample.hip and
+// capi_multi.hip (individual shards, site shards, groups and chains of handles) implement include/nghmm.h.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -99,6 +99,9 @@ struct nghmm_handle {
   size_t tseg_cap = 0;
   uint8_t* d_trec = nullptr;
   size_t trec_cap = 0;
+  // sampled paths (capi_sample.hip): maps, lane-chunk statistics, kept paths of one batch of draws
+  uint8_t* d_samp = nullptr;
+  size_t samp_cap = 0;
   uint32_t* d_passes = nullptr;
   double *d_freq_new = nullptr, *d_hap = nullptr;  // --freq_est 2 as intended: [S], [S][4]
 

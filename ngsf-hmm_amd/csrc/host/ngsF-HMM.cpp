@@ -9,7 +9,9 @@
 //
 // Extra options: --mode exact|fast (default fast), --device N, --ibd_bed [--ind_names FILE]
 // (PREFIX.ibd.bed: the IBD tracts of the .ibd path lines as scripts/convert_ibd.pl --ibd_pos
-// prints them, called on the device).  --n_threads (the
+// prints them, called on the device), --sample_paths R [--sample_seed N] [--sample_keep K]
+// (PREFIX.ibd.samples: the statistics of R IBD paths per individual drawn from the joint posterior
+// after the final decode; PREFIX.sample_kk.ibd: the first K of them).  --n_threads (the
 // reference's pool size) sets the host threads used for input normalisation and output
 // formatting; results do not depend on it.
 #include <fcntl.h>
@@ -40,6 +42,9 @@
 // referenced weakly: a build against a library without the tract entry still links, and
 // --ibd_bed then stops with a message
 #pragma weak nghmm_chain_ibd_tracts
+// ... and without the sampling entries: --sample_paths then stops with a message
+#pragma weak nghmm_sample_paths
+#pragma weak nghmm_chain_sample_paths
 
 namespace {
 
@@ -81,6 +86,11 @@ struct Params {  // ngsF-HMM.hpp:13-52
   bool ibd_bed = false;
   const char* in_ind_names = nullptr;
   std::vector<std::string> ind_names;
+  // --sample_paths R: R paths per individual from the joint posterior (nghmm_chain_sample_paths)
+  // after the final decode -> PREFIX.ibd.samples; --sample_keep K: the first K as
+  // PREFIX.sample_01.ibd ...; --sample_seed N: the generator's seed
+  unsigned sample_paths = 0, sample_keep = 0;
+  uint64_t sample_seed = 0;
   std::vector<uint64_t> site_pos;           // [S] the .pos file's integer positions
   std::vector<uint64_t> chrom_first;        // first site of every run of one chromosome name
   std::vector<std::string> chrom_name;      // ... and that name
@@ -1271,6 +1281,51 @@ void write_ibd_bed(const Params& P, Cohort& C) {
   if (fclose(fh) != 0) fatal(__FUNCTION__, "cannot write the IBD BED output file!");
 }
 
+// PREFIX.ibd.samples: one line "IND_ID draw ibd_sites n_tracts longest_sites ibd_mb" per individual
+// and draw (tab-separated, ordered by individual, then draw; IDs as --ibd_bed names them);
+// PREFIX.sample_kk.ibd: the path part of an .ibd file ("//" and one line of 0 / 1 per individual,
+// EM.cpp:338-345) for each of the first --sample_keep draws, which convert_ibd.pl --ibd_pos reads.
+void write_samples(const Params& P, Cohort& C) {
+  if (!nghmm_chain_sample_paths)
+    fatal(__FUNCTION__, "--sample_paths: the library has no nghmm_chain_sample_paths!");
+  const uint64_t I = P.n_ind, S = P.n_sites, R = P.sample_paths, K = P.sample_keep;
+  std::vector<nghmm_path_stats> st((size_t)R * I);
+  std::vector<uint8_t> paths((size_t)K * I * S);
+  check(nghmm_chain_sample_paths(C.hs.data(), C.n(), P.sample_seed, (uint32_t)R, st.data(), (uint32_t)K,
+                                 K ? paths.data() : nullptr),
+        "sample_paths");
+  const std::string name = P.prefix + ".ibd.samples";
+  FILE* fh = fopen(name.c_str(), "w");
+  if (!fh) fatal(__FUNCTION__, "cannot open sampled-path statistics output file!");
+  setvbuf(fh, nullptr, _IOFBF, 1 << 22);
+  for (uint64_t i = 0; i < I; i++) {
+    const std::string id = P.ind_names.empty() ? "ind" + std::to_string(i) : P.ind_names[i];
+    for (uint64_t d = 0; d < R; d++) {
+      const nghmm_path_stats& r = st[d * I + i];
+      fprintf(fh, "%s\t%llu\t%llu\t%llu\t%llu\t%.6f\n", id.c_str(), (unsigned long long)(d + 1),
+              (unsigned long long)r.ibd_sites, (unsigned long long)r.n_tracts,
+              (unsigned long long)r.longest_sites, r.ibd_mb);
+    }
+  }
+  if (fclose(fh) != 0) fatal(__FUNCTION__, "cannot write the sampled-path statistics output file!");
+  std::vector<char> line(S + 1);
+  for (uint64_t d = 0; d < K; d++) {
+    char tag[32];
+    snprintf(tag, sizeof tag, ".sample_%02llu.ibd", (unsigned long long)(d + 1));
+    FILE* fp = fopen((P.prefix + tag).c_str(), "w");
+    if (!fp) fatal(__FUNCTION__, "cannot open sampled-path output file!");
+    setvbuf(fp, nullptr, _IOFBF, 1 << 22);
+    fputs("//\n", fp);
+    for (uint64_t i = 0; i < I; i++) {
+      const uint8_t* z = &paths[(d * I + i) * S];
+      for (uint64_t s = 0; s < S; s++) line[s] = z[s] ? '1' : '0';
+      line[S] = '\n';
+      fwrite(line.data(), 1, S + 1, fp);
+    }
+    if (fclose(fp) != 0) fatal(__FUNCTION__, "cannot write a sampled-path output file!");
+  }
+}
+
 void sync_outputs(Params& P, Cohort& C, bool with_viterbi) {
   P.path.resize((size_t)P.n_ind * P.n_sites, 0);
   // indF / alpha are the cohort's on every handle; the frequencies those of its own sites
@@ -1304,6 +1359,8 @@ void parse_cmd_args(Params& P, int argc, char** argv) {  // parse_args.cpp:41-22
       {"devices", required_argument, nullptr, 1007},  {"ld_intended", no_argument, nullptr, 1008},
       {"parse_kat", no_argument, nullptr, 1009},
       {"ibd_bed", no_argument, nullptr, 1010},        {"ind_names", required_argument, nullptr, 1011},
+      {"sample_paths", required_argument, nullptr, 1012}, {"sample_seed", required_argument, nullptr, 1013},
+      {"sample_keep", required_argument, nullptr, 1014},
       {0, 0, 0, 0}};
   long taus_kat = 0;
   bool parse_kat = false;
@@ -1338,6 +1395,9 @@ void parse_cmd_args(Params& P, int argc, char** argv) {  // parse_args.cpp:41-22
       case 1009: parse_kat = true; break;
       case 1010: P.ibd_bed = true; break;
       case 1011: P.in_ind_names = optarg; break;
+      case 1012: P.sample_paths = (unsigned)atoi(optarg); break;
+      case 1013: P.sample_seed = strtoull(optarg, nullptr, 10); break;
+      case 1014: P.sample_keep = (unsigned)atoi(optarg); break;
       case 1000:
         if (!strcmp(optarg, "exact")) P.mode = NGHMM_MODE_EXACT;
         else if (!strcmp(optarg, "fast")) P.mode = NGHMM_MODE_FAST;
@@ -1412,6 +1472,10 @@ void parse_cmd_args(Params& P, int argc, char** argv) {  // parse_args.cpp:41-22
     warn(__FUNCTION__,
          "calculation of emission probabilities accounting for LD is still under development!");
   if (!P.out_prefix) fatal(__FUNCTION__, "output prefix (--out) missing!");
+  if (P.sample_keep > P.sample_paths)
+    fatal(__FUNCTION__, "--sample_keep is larger than --sample_paths!");
+  if (P.sample_paths && !nghmm_chain_sample_paths)
+    fatal(__FUNCTION__, "--sample_paths: the library has no nghmm_chain_sample_paths!");
   if (P.min_iters < 1 || P.max_iters < 1 || P.min_iters >= P.max_iters)
     fatal(__FUNCTION__, "invalid number of iterations!");
   if (P.n_threads < 1) fatal(__FUNCTION__, "invalid number of threads!");
@@ -1443,7 +1507,7 @@ void parse_cmd_args(Params& P, int argc, char** argv) {  // parse_args.cpp:41-22
     gzclose(fh);
     if (P.ind_names.size() != P.n_ind)
       fatal(__FUNCTION__, "number of lines in --ind_names file is not --n_ind!");
-    if (!P.ibd_bed) warn(__FUNCTION__, "--ind_names is only used by --ibd_bed");
+    if (!P.ibd_bed && !P.sample_paths) warn(__FUNCTION__, "--ind_names is only used by --ibd_bed and --sample_paths");
   }
   P.prefix = P.out_prefix;
 }
@@ -1536,6 +1600,7 @@ void finish_run(Params& P, Cohort& C) {
     fprintf(P.out, "Printing final results\n");
   }
   print_iter(P, C);
+  if (P.sample_paths) write_samples(P, C);
   if (P.verbose >= 2)  // (not a line of the reference's)
     fprintf(P.out, "> decoded in %.2f s, output files written in %.2f s\n", t1 - t0, omp_get_wtime() - t1);
 }
@@ -1656,8 +1721,15 @@ int main(int argc, char** argv) {
       free(bufs[r]);
     }
     if (P.keep_starts) {  // the script moves the best replicate's files to the output prefix
-      for (const char* ext : {".indF", ".ibd", ".geno", ".ibd.bed"}) {
-        if (!P.ibd_bed && !strcmp(ext, ".ibd.bed")) continue;
+      std::vector<std::string> exts = {".indF", ".ibd", ".geno"};
+      if (P.ibd_bed) exts.push_back(".ibd.bed");
+      if (P.sample_paths) exts.push_back(".ibd.samples");
+      for (unsigned k = 1; P.sample_paths && k <= P.sample_keep; k++) {
+        char tag[32];
+        snprintf(tag, sizeof tag, ".sample_%02u.ibd", k);
+        exts.push_back(tag);
+      }
+      for (const std::string& ext : exts) {
         const std::string from = runs[best].prefix + ext, to = std::string(P.out_prefix) + ext;
         FILE* a = fopen(from.c_str(), "rb");
         FILE* b = fopen(to.c_str(), "wb");

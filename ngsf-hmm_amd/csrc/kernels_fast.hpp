@@ -236,6 +236,8 @@ bool fast_lkl_launch_planned(FastState& fs, hipStream_t st, const void* d_groups
 // vectors, backward sweep with posteriors into fs.post (tile-major)
 bool fast_estep(FastState& fs, hipStream_t st, const double* d_indF, const double* d_alpha,
                 double* d_ind_lkl, int* d_flags, bool have_forward_walk);
+// the forward walk of fast_estep alone: lane-chunk operators and checkpoints at (d_indF, d_alpha)
+bool fast_forward_ops(FastState& fs, hipStream_t st, const double* d_indF, const double* d_alpha);
 // fs.post -> site-major [S][I]
 bool fast_post_to_site_major(FastState& fs, hipStream_t st, double* d_marg);
 // out = exp(in) elementwise (in == out allowed): linear genotype likelihoods

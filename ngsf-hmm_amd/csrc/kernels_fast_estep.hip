@@ -644,6 +644,15 @@ bool fast_estep(FastState& fs, hipStream_t st, const double* d_indF, const doubl
   return hipGetLastError() == hipSuccess;
 }
 
+// phase A alone (kernels_sample.hpp: a call that samples paths needs the lane-chunk operators and
+// checkpoints of the CURRENT parameters, whatever the last E-step ran with)
+bool fast_forward_ops(FastState& fs, hipStream_t st, const double* d_indF, const double* d_alpha) {
+  hipLaunchKernelGGL(k_fast_chunk_ops, dim3((unsigned)(fs.I * fs.C)), dim3(64), 0, st, fs.e_il,
+                     fs.pos_il, fs.T, fs.C, d_indF, d_alpha,
+                     EmitPtrs{fs.lane_ops, reinterpret_cast<double2*>(fs.ckpt)});
+  return hipGetLastError() == hipSuccess;
+}
+
 bool fast_post_to_site_major(FastState& fs, hipStream_t st, double* d_marg) {
   const uint64_t n_it = (fs.I + 63) / 64;
   const dim3 grid((unsigned)((uint64_t)fs.C * fs.T * n_it)), block(256);

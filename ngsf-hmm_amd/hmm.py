@@ -143,6 +143,9 @@ def load_library():
                                            C.POINTER(C.c_uint8)]),
         "nghmm_ibd_tracts": (i32, [vp, i32, d, u64, vp, u64, C.POINTER(u64)]),
         "nghmm_chain_ibd_tracts": (i32, [C.POINTER(vp), i32, i32, d, u64, vp, u64, C.POINTER(u64)]),
+        "nghmm_sample_paths": (i32, [vp, u64, u32, vp, u32, C.POINTER(C.c_uint8)]),
+        "nghmm_chain_sample_paths": (i32, [C.POINTER(vp), i32, u64, u32, vp, u32,
+                                           C.POINTER(C.c_uint8)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -179,6 +182,7 @@ EXPORTED_SYMBOLS = [
     "nghmm_viterbi_shard_back", "nghmm_chain_setup", "nghmm_chain_iter_em", "nghmm_chain_mstep_freq",
     "nghmm_chain_viterbi", "nghmm_alloc_host", "nghmm_free_host",
     "nghmm_ibd_tracts", "nghmm_chain_ibd_tracts",
+    "nghmm_sample_paths", "nghmm_chain_sample_paths",
 ]
 
 OBJECTIVE_FN = C.CFUNCTYPE(C.c_double, C.c_uint32, C.c_double, C.c_double, C.c_void_p)
@@ -261,6 +265,28 @@ def bed_lines(tracts, chrom_names, positions, ind_names):
         start, end = int(positions[a]) - 1, int(positions[b])
         lines.append(f"{chrom_names[a]}\t{start}\t{end}\t{ind_names[int(t['ind'])]}\t{end - start}\n")
     return "".join(lines)
+
+
+# nghmm_path_stats (include/nghmm.h): one record per (draw, individual) of sample_paths
+PATH_STATS_DTYPE = np.dtype([("ibd_sites", np.uint64), ("n_tracts", np.uint64),
+                             ("longest_sites", np.uint64), ("ibd_mb", np.float64)])
+
+
+def _sample_paths(call, check, n_ind, n_sites, n_draws, seed, keep):
+    n_draws, keep = int(n_draws), int(keep)
+    if n_draws < 0 or keep < 0 or n_draws >= 2 ** 32 or keep >= 2 ** 32:
+        raise NgsFHMMError(-10, f"sample_paths: n_draws = {n_draws}, keep = {keep}")
+    stats = np.zeros((n_draws, n_ind), dtype=PATH_STATS_DTYPE)
+    paths = np.zeros((keep, n_ind, n_sites), dtype=np.uint8)
+    check(call(int(seed) & (2 ** 64 - 1), n_draws, C.c_void_p(stats.ctypes.data), keep,
+               paths.ctypes.data_as(C.POINTER(C.c_uint8)) if keep else None))
+    return stats, paths
+
+
+def path_stats_summary(stats, q=(0.025, 0.5, 0.975)):
+    """Per-individual quantiles over the draws of every field of sample_paths' records:
+    {field: array [len(q)][I]}."""
+    return {f: np.quantile(stats[f].astype(np.float64), q, axis=0) for f in PATH_STATS_DTYPE.names}
 
 
 KERNEL_SLOTS = {"emission": 0, "forward": 1, "backward": 2, "lkl_batch": 3, "est_maf": 4,
@@ -634,6 +660,14 @@ class NgsFHMM:
         return _tracts(lambda *a: self.lib.nghmm_ibd_tracts(self._h, *a), self._check, source,
                        threshold, min_sites)
 
+    def sample_paths(self, n_draws, seed=0, keep=0):
+        """n_draws IBD paths per individual drawn from the joint posterior P(z | data, theta) at
+        the current parameters (nghmm_sample_paths).  Returns (stats, paths): a structured array
+        [n_draws][I] of PATH_STATS_DTYPE and the first `keep` draws as uint8 [keep][I][S].  Draw d
+        depends on (seed, d) alone."""
+        return _sample_paths(lambda *a: self.lib.nghmm_sample_paths(self._h, *a), self._check,
+                             self.n_ind, self.n_sites, n_draws, seed, keep)
+
     # -- measurement -------------------------------------------------------
     def kernel_ms(self, name):
         """(milliseconds, launches) of a kernel family in the last call that ran it.  Fast mode's
@@ -751,6 +785,14 @@ class Chain:
         self._members_open()
         return _tracts(lambda *a: self.lib.nghmm_chain_ibd_tracts(self._arr, len(self.handles), *a),
                        self.handles[0]._check, source, threshold, min_sites)
+
+    def sample_paths(self, n_draws, seed=0, keep=0):
+        """NgsFHMM.sample_paths over the chain (nghmm_chain_sample_paths): the single handle's
+        draws, global site indices."""
+        self._members_open()
+        return _sample_paths(
+            lambda *a: self.lib.nghmm_chain_sample_paths(self._arr, len(self.handles), *a),
+            self.handles[0]._check, self.n_ind, self.n_sites, n_draws, seed, keep)
 
     @property
     def freq(self):
