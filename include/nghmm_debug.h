@@ -40,6 +40,10 @@ extern "C" {
  *                     0: backward sweep and est_maf after the rounds)
  *   exact_serial      1: exact-mode recursions as one lane per chain (kernels_exact.hip) instead of
  *                     producer-consumer workgroups (kernels_exact_pc.hip): the same bits
+ *   viterbi_chunk     n > 0: the Viterbi forward sweep hands its scores on every n sites -- n rounded down
+ *                     to a multiple of 16, at least 16, never more than the default -- instead of every
+ *                     2 GiB of transition logs (default 0: 2^31 / (32 individuals) sites, 67 104 at 1000
+ *                     individuals); may change between two decodes of a handle: the same path
  *   dbg_abort_round   test hook: a device-planned M-step returns an error after this round
  * Fixed at creation (environment only): fast_c (waves per individual).  Unknown names return
  * NGHMM_ERR_ARG.  Outside the handle: NGHMM_HOST_THREADS (host threads of the L-BFGS-B state

@@ -194,6 +194,11 @@ int ensure_points(nghmm_t* h, size_t n);
 GlView own_gl(const nghmm_t* h);
 int ensure_tmp(nghmm_t* h);
 int ensure_marg(nghmm_t* h);
+// Scratch of the Viterbi forward sweep (d_vit), allocated once for the default chunk; *chunk = the
+// sites per chunk of this decode (switch viterbi_chunk: never more than the default), *state = the
+// carried scores [I][2], which sit behind THAT chunk's transition logs (where
+// launch_viterbi_fwd_exact, given *chunk, reads and leaves them)
+int viterbi_scratch(nghmm_t* h, uint64_t* chunk, double** state = nullptr);
 int fast_estep_impl(nghmm_t* h, double* ind_lkl, bool have_walk);
 int redo_nonfinite(nghmm_t* h, uint32_t n_pts, const uint32_t* ind, const double* F,
                    const double* alpha, double* lkl);

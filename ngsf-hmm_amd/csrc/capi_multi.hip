@@ -81,9 +81,9 @@ int nghmm_viterbi_shard_forward(nghmm_t* h, const double* scores_in, double* sco
   if (!h->d_bp && (rc = dev_alloc(&h->d_bp, blocked + h->I))) return rc;
   if (!h->d_path_sites && (rc = dev_alloc(&h->d_path_sites, blocked))) return rc;
   if (!h->d_path && (rc = dev_alloc(&h->d_path, (size_t)h->I * h->S))) return rc;
-  const uint64_t chunk = viterbi_chunk_sites(h->S, h->I);
-  if (!h->d_vit && (rc = dev_alloc(&h->d_vit, (size_t)chunk * h->I * 4 + h->I * 2))) return rc;
-  double* d_state = h->d_vit + (size_t)chunk * h->I * 4;
+  uint64_t chunk;
+  double* d_state;
+  if ((rc = viterbi_scratch(h, &chunk, &d_state))) return rc;
   if (scores_in)
     HIP_TRY(hipMemcpyAsync(d_state, scores_in, h->I * 2 * sizeof(double), hipMemcpyHostToDevice,
                            h->stream));

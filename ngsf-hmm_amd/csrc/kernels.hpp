@@ -100,7 +100,8 @@ void launch_emission_ld_exact(hipStream_t st, const GlView& gl, const double* fr
 
 // Viterbi (shared/HMM.cpp:98-125): bp [viterbi_blocked_bytes + I] scratch bytes, path_sites
 // [viterbi_blocked_bytes] bytes blocked [site/16][I][16] (launch_unblock_path gives [I][S]),
-// scratch [chunk_sites*I*4 + I*2] doubles (chunk_sites from viterbi_chunk_sites)
+// scratch [chunk_sites*I*4 + I*2] doubles (chunk_sites from viterbi_chunk_sites; forced > 0: the
+// switch viterbi_chunk, rounded down to a multiple of 16, at least 16, at most the default)
 // the two halves of launch_viterbi_exact, for a handle whose sites continue another's (a site
 // shard): chain_start false = scratch's state doubles hold the scores the range before ended
 // with; the I last-state bytes behind bp may be overwritten between the halves; state_before
@@ -114,7 +115,7 @@ void launch_viterbi_back_exact(hipStream_t st, uint8_t* bp, uint64_t S, uint64_t
 void launch_viterbi_exact(hipStream_t st, const double* eprob, const double* pos, uint64_t S,
                           uint64_t I, const double* indF, const double* alpha, uint8_t* bp,
                           uint8_t* path_sites, double* scratch, uint64_t chunk_sites, bool serial = false);
-uint64_t viterbi_chunk_sites(uint64_t S, uint64_t I);
+uint64_t viterbi_chunk_sites(uint64_t S, uint64_t I, int64_t forced = 0);
 uint64_t viterbi_blocked_bytes(uint64_t S, uint64_t I);
 void launch_unblock_path(hipStream_t st, const uint8_t* path16, uint64_t S, uint64_t I,
                          uint8_t* out);

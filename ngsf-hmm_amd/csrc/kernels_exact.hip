@@ -1006,13 +1006,18 @@ void launch_unblock_path(hipStream_t st, const uint8_t* path16, uint64_t S, uint
   hipLaunchKernelGGL(k_unblock_path, dim3(4096), dim3(256), 0, st, path16, S, I, out);
 }
 
-uint64_t viterbi_chunk_sites(uint64_t S, uint64_t I) {
+uint64_t viterbi_chunk_sites(uint64_t S, uint64_t I, int64_t forced) {
   // about 2 GiB of transition logs per chunk; a multiple of 16 (blocked back-pointers)
   uint64_t ch = (2ull << 30) / (I * 32);
   ch &= ~15ull;
   if (ch < 64) ch = 64;
   const uint64_t Sp = (S + 15) & ~15ull;
-  return ch < Sp ? ch : Sp;
+  if (ch > Sp) ch = Sp;
+  if (forced <= 0) return ch;
+  // switch viterbi_chunk: shorter chunks only, so that a scratch sized for the default holds them
+  uint64_t n = (uint64_t)forced & ~15ull;
+  if (n < 16) n = 16;
+  return n < ch ? n : ch;
 }
 
 uint64_t viterbi_blocked_bytes(uint64_t S, uint64_t I) { return ((S + 15) / 16) * 16 * I; }

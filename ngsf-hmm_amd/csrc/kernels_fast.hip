@@ -269,7 +269,8 @@ const SwitchName kSwitches[] = {
     {"estmaf_no_rows", &Switches::estmaf_no_rows}, {"estmaf_no_called", &Switches::estmaf_no_called},
     {"fast_c", &Switches::fast_c}, {"exact_serial", &Switches::exact_serial},
     {"dbg_abort_round", &Switches::dbg_abort_round}, {"no_dev_bfgs", &Switches::no_dev_bfgs},
-    {"no_bg_stream", &Switches::no_bg_stream}, {"spans", &Switches::spans}};
+    {"no_bg_stream", &Switches::no_bg_stream}, {"spans", &Switches::spans},
+    {"viterbi_chunk", &Switches::viterbi_chunk}};
 
 }  // namespace
 

@@ -126,6 +126,15 @@ int ensure_tmp(nghmm_t* h) {
   return dev_alloc(&h->d_tmp, h->S * h->I * 2);
 }
 
+int viterbi_scratch(nghmm_t* h, uint64_t* chunk, double** state) {
+  int rc;
+  const uint64_t room = viterbi_chunk_sites(h->S, h->I);
+  if (!h->d_vit && (rc = dev_alloc(&h->d_vit, (size_t)room * h->I * 4 + h->I * 2))) return rc;
+  *chunk = viterbi_chunk_sites(h->S, h->I, h->fast.sw.viterbi_chunk);
+  if (state) *state = h->d_vit + (size_t)*chunk * h->I * 4;
+  return NGHMM_OK;
+}
+
 int ensure_emissions(nghmm_t* h);
 
 // site-major posteriors [S][I] in d_marg (fast mode: converted from the tile-major layout)
@@ -1672,8 +1681,8 @@ int nghmm_viterbi(nghmm_t* h, uint8_t* path) {
   if (!h->d_bp && (rc = dev_alloc(&h->d_bp, blocked + h->I))) return rc;
   if (!h->d_path_sites && (rc = dev_alloc(&h->d_path_sites, blocked))) return rc;
   if (!h->d_path && (rc = dev_alloc(&h->d_path, cells))) return rc;
-  const uint64_t chunk = viterbi_chunk_sites(h->S, h->I);
-  if (!h->d_vit && (rc = dev_alloc(&h->d_vit, (size_t)chunk * h->I * 4 + h->I * 2))) return rc;
+  uint64_t chunk;
+  if ((rc = viterbi_scratch(h, &chunk))) return rc;
   tic(h);
   if (h->mode == NGHMM_MODE_FAST) {
     if ((rc = clear_flags(h))) return rc;

@@ -364,8 +364,8 @@ static int array_max_pos(const double* a, int n) {
 
 /* shared/HMM.cpp:98-125.  Vi_prob is updated in place inside the l loop, so
  * state 1 at site s reads state 0's value for site s (reference behaviour). */
-double orc_viterbi(const double q[2], double alpha, const double* e_prob, const double* pos_dist,
-                   uint64_t S, char* path) {
+static double viterbi_impl(const double q[2], double alpha, const double* e_prob,
+                           const double* pos_dist, uint64_t S, char* path, uint8_t* back_out) {
   double Vi_prob[2];
   uint8_t* back = (uint8_t*)malloc(2 * (S + 1));
   for (int k = 0; k < 2; k++) Vi_prob[k] = ORC_LOG(q[k]);
@@ -387,8 +387,15 @@ double orc_viterbi(const double q[2], double alpha, const double* e_prob, const 
   path[S] = (char)array_max_pos(Vi_prob, 2);
   for (uint64_t s = S; s > 0; s--) path[s - 1] = (char)back[2 * s + (int)path[s]];
   double r = Vi_prob[(int)path[S]];
+  if (back_out) /* per site: the predecessor chosen for state 0 in bit 0, for state 1 in bit 1 */
+    for (uint64_t s = 1; s <= S; s++) back_out[s - 1] = (uint8_t)(back[2 * s] | (back[2 * s + 1] << 1));
   free(back);
   return r;
+}
+
+double orc_viterbi(const double q[2], double alpha, const double* e_prob, const double* pos_dist,
+                   uint64_t S, char* path) {
+  return viterbi_impl(q, alpha, e_prob, pos_dist, S, path, NULL);
 }
 
 /* EM.cpp:449-464 */
@@ -708,13 +715,17 @@ int orc_em_run(orc_em* em, int freq_est, int indF_fixed, int alpha_fixed, int mi
 
 /* EM.cpp:105-116 */
 int orc_em_viterbi(orc_em* em, uint8_t* path, int n_threads) {
+  return orc_em_viterbi_back(em, path, NULL, n_threads);
+}
+
+int orc_em_viterbi_back(orc_em* em, uint8_t* path, uint8_t* back, int n_threads) {
   const uint64_t I = em->I, S = em->S;
   if (n_threads < 1) n_threads = 1;
 #pragma omp parallel for num_threads(n_threads) schedule(dynamic, 1)
   for (uint64_t i = 0; i < I; i++) {
     char* p = (char*)malloc(S + 1);
     double q[2] = {1 - em->indF[i], em->indF[i]};
-    orc_viterbi(q, em->alpha[i], em->e_prob + i * S * 2, em->pos_dist, S, p);
+    viterbi_impl(q, em->alpha[i], em->e_prob + i * S * 2, em->pos_dist, S, p, back ? back + i * S : NULL);
     for (uint64_t s = 0; s < S; s++) path[i * S + s] = (uint8_t)p[s + 1];
     free(p);
   }

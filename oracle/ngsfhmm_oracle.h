@@ -151,6 +151,9 @@ int orc_em_run(orc_em* em, int freq_est, int indF_fixed, int alpha_fixed, int mi
                int max_iters, double min_epsilon, int n_threads);
 /* EM.cpp:105-116: Viterbi for every individual; path = [I][S] bytes 0/1 */
 int orc_em_viterbi(orc_em* em, uint8_t* path, int n_threads);
+/* the same, and the back-pointers it walked (back may be NULL): back = [I][S] bytes, bit l = the
+ * predecessor HMM.cpp:105-116 chose for state l at that site */
+int orc_em_viterbi_back(orc_em* em, uint8_t* path, uint8_t* back, int n_threads);
 /* EM.cpp:367-376: genotype posteriors [S][I][3] given a path [I][S] */
 void orc_em_geno_post(orc_em* em, const uint8_t* path, double* out);
 

@@ -79,6 +79,7 @@ class Oracle:
             "orc_calc_emission_ld": (d, [dp, dp, dp, d, d, i32, ip]),
             "orc_em_run": (i32, [C.c_void_p, i32, i32, i32, i32, i32, d, i32]),
             "orc_em_viterbi": (i32, [C.c_void_p, C.POINTER(C.c_uint8), i32]),
+            "orc_em_viterbi_back": (i32, [C.c_void_p, C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), i32]),
             "orc_em_geno_post": (None, [C.c_void_p, C.POINTER(C.c_uint8), dp]),
             "orc_em_indF": (dp, [C.c_void_p]), "orc_em_alpha": (dp, [C.c_void_p]),
             "orc_em_freq": (dp, [C.c_void_p]), "orc_em_ind_lkl": (dp, [C.c_void_p]),
@@ -259,6 +260,15 @@ class OracleEM:
         path = np.empty((self.I, self.S), dtype=np.uint8)
         self.orc.lib.orc_em_viterbi(self.h, path.ctypes.data_as(C.POINTER(C.c_uint8)), n_threads)
         return path
+
+    def viterbi_back(self, n_threads=1):
+        """(path [I][S], back-pointers [I][S]: bit l = the predecessor chosen for state l)."""
+        path = np.empty((self.I, self.S), dtype=np.uint8)
+        back = np.empty((self.I, self.S), dtype=np.uint8)
+        u8p = C.POINTER(C.c_uint8)
+        self.orc.lib.orc_em_viterbi_back(self.h, path.ctypes.data_as(u8p), back.ctypes.data_as(u8p),
+                                         n_threads)
+        return path, back
 
     def geno_post(self, path):
         path = np.ascontiguousarray(path, dtype=np.uint8)
