@@ -345,6 +345,46 @@ int nghmm_sample_paths(nghmm_t* h, uint64_t seed, uint32_t n_draws, nghmm_path_s
 int nghmm_chain_sample_paths(nghmm_t** hs, int n, uint64_t seed, uint32_t n_draws,
                              nghmm_path_stats* stats, uint32_t n_keep, uint8_t* paths);
 
+/* ---- observed information of indF and alpha ----
+ * Per individual the log-likelihood, its gradient and its 2x2 Hessian in (F, alpha) at one point,
+ * from EXACT derivatives carried through one forward pass (no finite differences): what standard
+ * errors of the two estimates, their correlation, and a convergence diagnostic (the gradient at
+ * the final parameters) are made of.  (The reference has no such function.)
+ *
+ * Definition.  l_i(F, alpha) is the forward log-likelihood of individual i that nghmm_lkl_batch
+ * defines: under the handle's CURRENT EMISSIONS, with q = (1 - F, F) and c_s = exp(-alpha d_s)
+ * (0 where d_s = +inf: a chromosome start).  A site is the operator M_s = (c_s I + (1 - c_s) 1 q^T)
+ * diag(e_s), l_i = log(q prod_s M_s 1); the product rule carries dM/dF, dM/dalpha and the three
+ * second derivatives along with the product.  THE ALLELE FREQUENCIES ARE HELD FIXED: the
+ * emissions do not move with (F, alpha), so standard errors derived from these records are
+ * CONDITIONAL ON THE FREQUENCIES (they ignore the uncertainty of the frequency estimates and
+ * are, if anything, too small).
+ *
+ * g_* and h_* are the first and second partial derivatives of l_i itself, not of -l_i: the
+ * observed information is -h.  h_xy is formed as Z_xy / Z - g_x g_y (Z the likelihood), which
+ * loses about eps |g_x g_y / h_xy| to cancellation far from an optimum.
+ * No float atomics: one order of operations, the same bits on every call. */
+typedef struct nghmm_info {  /* 48 bytes */
+  double lkl;                /* l_i */
+  double g_F, g_A;           /* dl/dF, dl/dalpha */
+  double h_FF, h_FA, h_AA;   /* d2l/dF2, d2l/dF dalpha, d2l/dalpha2 */
+} nghmm_info;
+#ifdef __cplusplus
+static_assert(sizeof(nghmm_info) == 48, "nghmm_info is six doubles");
+#endif
+/* out[I] (host).  F and alpha are host [I] arrays: the point of every individual; NULL for BOTH
+ * means the handle's current parameters.  NGHMM_ERR_ARG for exactly one NULL, for a point outside
+ * the box of EM.cpp:424-438 (F in [1e-15, 1 - 1e-15], alpha in [1e-15, 10]) or NaN, for out ==
+ * NULL, for a handle without data.  Self-contained like nghmm_viterbi and nghmm_sample_paths: it
+ * refreshes stale emissions itself and leaves parameters, posteriors, the Viterbi path,
+ * checkpoints and an M-step planned in advance untouched. */
+int nghmm_obs_info(nghmm_t* h, const double* F, const double* alpha, nghmm_info* out);
+/* The same over a chain of site shards (nghmm_chain_setup, else NGHMM_ERR_ARG): every shard
+ * reduces its site range to one jet per individual (24 doubles and an exponent), the host
+ * multiplies them in rank order and closes once.  (Chains of more than one handle are fast mode
+ * only.) */
+int nghmm_chain_obs_info(nghmm_t** hs, int n, const double* F, const double* alpha, nghmm_info* out);
+
 /* ---- multi-GPU (individuals sharded over ranks) ----
  * The allele-frequency step needs every individual of a site.  A rank owns the
  * individuals [ind_begin, ind_begin + n_ind) of n_ind_total for all sites, and

@@ -17,9 +17,9 @@ an :class:`NgsFHMM` raises.
 from .hmm import (NgsFHMM, NgsFHMMError, Group, Chain, MODE_EXACT, MODE_FAST, GENO_PACKED, LD_INTENDED, EPROB_LD, library_path,
                   load_library,
                   build_library, bed_lines, TRACTS_VITERBI, TRACTS_POSTERIOR, PATH_STATS_DTYPE,
-                  path_stats_summary)
+                  path_stats_summary, INFO_DTYPE, std_errors)
 from . import simulate
 
 __all__ = ["NgsFHMM", "NgsFHMMError", "Group", "Chain", "MODE_EXACT", "MODE_FAST", "GENO_PACKED", "LD_INTENDED", "EPROB_LD", "library_path",
            "load_library", "build_library", "simulate", "bed_lines", "TRACTS_VITERBI", "TRACTS_POSTERIOR",
-           "PATH_STATS_DTYPE", "path_stats_summary"]
+           "PATH_STATS_DTYPE", "path_stats_summary", "INFO_DTYPE", "std_errors"]

@@ -1,6 +1,6 @@
 // capi_internal.hpp -- what the translation units of the C ABI share: the handle, error plumbing,
 // and the helpers every entry point uses.  nghmm_capi.hip (handle life cycle, single-handle EM),
-// capi_load.hip (loaders), capi_output.hip (read-back and output formatting), capi_tracts.hip, capi_sample.hip and
+// capi_load.hip (loaders), capi_output.hip (read-back and output formatting), capi_tracts.hip, capi_sample.hip, capi_info.hip and
 // capi_multi.hip (individual shards, site shards, groups and chains of handles) implement include/nghmm.h.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -102,6 +102,9 @@ struct nghmm_handle {
   // sampled paths (capi_sample.hip): maps, lane-chunk statistics, kept paths of one batch of draws
   uint8_t* d_samp = nullptr;
   size_t samp_cap = 0;
+  // observed information (capi_info.hip): the points, the waves' jets, the records
+  uint8_t* d_info = nullptr;
+  size_t info_cap = 0;
   uint32_t* d_passes = nullptr;
   double *d_freq_new = nullptr, *d_hap = nullptr;  // --freq_est 2 as intended: [S], [S][4]
 
@@ -233,6 +236,18 @@ int dev_alloc(T** p, size_t n) {
     set_error("hipMalloc of %zu bytes failed: %s", n * sizeof(T), hipGetErrorString(e));
     return NGHMM_ERR_NOMEM;
   }
+  return NGHMM_OK;
+}
+
+// a scratch buffer of the handle that grows on demand (its contents are not kept)
+inline int grow(uint8_t** p, size_t* cap, size_t bytes) {
+  if (bytes <= *cap) return NGHMM_OK;
+  if (*p) (void)hipFree(*p);
+  *p = nullptr;
+  *cap = 0;
+  int rc;
+  if ((rc = dev_alloc(p, bytes))) return rc;
+  *cap = bytes;
   return NGHMM_OK;
 }
 

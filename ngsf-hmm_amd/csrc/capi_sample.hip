@@ -11,17 +11,6 @@ static_assert(sizeof(nghmm_path_stats) == 32, "nghmm_path_stats is 32 bytes");
 
 namespace {
 
-int grow(uint8_t** p, size_t* cap, size_t bytes) {
-  if (bytes <= *cap) return NGHMM_OK;
-  if (*p) (void)hipFree(*p);
-  *p = nullptr;
-  *cap = 0;
-  int rc;
-  if ((rc = dev_alloc(p, bytes))) return rc;
-  *cap = bytes;
-  return NGHMM_OK;
-}
-
 nghmm_path_stats seg_stats(const SampleSeg& s) {
   nghmm_path_stats o;
   o.ibd_sites = s.ones;

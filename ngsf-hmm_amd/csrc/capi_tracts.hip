@@ -41,17 +41,6 @@ int tracts_check_args(nghmm_t* h, int source, double threshold, const char* who)
 
 namespace {
 
-int grow(uint8_t** p, size_t* cap, size_t bytes) {
-  if (bytes <= *cap) return NGHMM_OK;
-  if (*p) (void)hipFree(*p);
-  *p = nullptr;
-  *cap = 0;
-  int rc;
-  if ((rc = dev_alloc(p, bytes))) return rc;
-  *cap = bytes;
-  return NGHMM_OK;
-}
-
 // The passes on the handle's stream; *d_out = the records on the device, *n_out = their number.
 // Arguments checked by the caller.
 int tracts_device(nghmm_t* h, int source, double thr, uint64_t min_sites, const TractRec** d_out,

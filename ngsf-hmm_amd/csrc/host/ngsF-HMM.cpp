@@ -11,7 +11,9 @@
 // (PREFIX.ibd.bed: the IBD tracts of the .ibd path lines as scripts/convert_ibd.pl --ibd_pos
 // prints them, called on the device), --sample_paths R [--sample_seed N] [--sample_keep K]
 // (PREFIX.ibd.samples: the statistics of R IBD paths per individual drawn from the joint posterior
-// after the final decode; PREFIX.sample_kk.ibd: the first K of them).  --n_threads (the
+// after the final decode; PREFIX.sample_kk.ibd: the first K of them), --indF_se (PREFIX.indF.se:
+// standard errors of indF and alpha from the observed information at the final parameters,
+// conditional on the allele frequencies).  --n_threads (the
 // reference's pool size) sets the host threads used for input normalisation and output
 // formatting; results do not depend on it.
 #include <fcntl.h>
@@ -45,6 +47,8 @@
 // ... and without the sampling entries: --sample_paths then stops with a message
 #pragma weak nghmm_sample_paths
 #pragma weak nghmm_chain_sample_paths
+// ... and without the observed-information entry: --indF_se then stops with a message
+#pragma weak nghmm_chain_obs_info
 
 namespace {
 
@@ -91,6 +95,10 @@ struct Params {  // ngsF-HMM.hpp:13-52
   // PREFIX.sample_01.ibd ...; --sample_seed N: the generator's seed
   unsigned sample_paths = 0, sample_keep = 0;
   uint64_t sample_seed = 0;
+  // --indF_se: PREFIX.indF.se after the final decode -- standard errors of indF and alpha and
+  // their correlation from the observed information at the final parameters and frequencies
+  // (nghmm_chain_obs_info), the log-likelihood and its gradient there
+  bool indF_se = false;
   std::vector<uint64_t> site_pos;           // [S] the .pos file's integer positions
   std::vector<uint64_t> chrom_first;        // first site of every run of one chromosome name
   std::vector<std::string> chrom_name;      // ... and that name
@@ -1326,6 +1334,68 @@ void write_samples(const Params& P, Cohort& C) {
   }
 }
 
+// Standard errors from the Hessian h of the log-likelihood in (indF, alpha) at the estimates; the
+// rule is the one std_errors of the Python package states (tests hold the two to each other):
+// a parameter on its bound is fixed (se NaN, out of the inversion) -- indF < 1e-5 or > 1 - 1e-5,
+// the .indF file's NA rule (EM.cpp:293-310), alpha <= 1e-15 or >= 10 --; indF on its bound makes
+// all three NaN (alpha is unidentified); a free block of -h that is not positive definite gives
+// NaN; else se = sqrt diag((-h)^-1) over the free parameters, corr from its off-diagonal.
+struct SeOut {
+  double se_F = NAN, se_A = NAN, corr = NAN;
+};
+SeOut se_rule(double F, double A, double h_FF, double h_FA, double h_AA) {
+  SeOut o;
+  if (F < kEPSILON || F > 1 - kEPSILON) return o;
+  const double a = -h_FF, b = -h_FA, d = -h_AA;
+  if (A <= 1e-15 || A >= 10.0) {
+    if (a > 0) o.se_F = sqrt(1.0 / a);
+    return o;
+  }
+  const double det = a * d - b * b;
+  if (a > 0 && det > 0) {
+    o.se_F = sqrt(d / det);
+    o.se_A = sqrt(a / det);
+    o.corr = -b / sqrt(a * d);
+  }
+  return o;
+}
+
+// "%.10g", NaN as NA
+void put_g(FILE* fh, double v, char end) {
+  if (std::isnan(v)) fprintf(fh, "NA%c", end);
+  else fprintf(fh, "%.10g%c", v, end);
+}
+
+// PREFIX.indF.se: a header line, then per individual "IND_ID indF se_indF alpha se_alpha corr lkl
+// grad_indF grad_alpha" (tab-separated; IDs as --ibd_bed names them), at the final parameters and
+// frequencies; the standard errors are conditional on the frequencies (include/nghmm.h).
+void write_indF_se(const Params& P, Cohort& C) {
+  if (!nghmm_chain_obs_info)
+    fatal(__FUNCTION__, "--indF_se: the library has no nghmm_chain_obs_info!");
+  const uint64_t I = P.n_ind;
+  std::vector<nghmm_info> rec(I);
+  check(nghmm_chain_obs_info(C.hs.data(), C.n(), nullptr, nullptr, rec.data()), "obs_info");
+  const std::string name = P.prefix + ".indF.se";
+  FILE* fh = fopen(name.c_str(), "w");
+  if (!fh) fatal(__FUNCTION__, "cannot open standard-error output file!");
+  fputs("ind\tindF\tse_indF\talpha\tse_alpha\tcorr\tlkl\tgrad_indF\tgrad_alpha\n", fh);
+  for (uint64_t i = 0; i < I; i++) {
+    const std::string id = P.ind_names.empty() ? "ind" + std::to_string(i) : P.ind_names[i];
+    const nghmm_info& r = rec[i];
+    const SeOut se = se_rule(P.indF[i], P.alpha[i], r.h_FF, r.h_FA, r.h_AA);
+    fprintf(fh, "%s\t", id.c_str());
+    put_g(fh, P.indF[i], '\t');
+    put_g(fh, se.se_F, '\t');
+    put_g(fh, P.alpha[i], '\t');
+    put_g(fh, se.se_A, '\t');
+    put_g(fh, se.corr, '\t');
+    put_g(fh, r.lkl, '\t');
+    put_g(fh, r.g_F, '\t');
+    put_g(fh, r.g_A, '\n');
+  }
+  if (fclose(fh) != 0) fatal(__FUNCTION__, "cannot write the standard-error output file!");
+}
+
 void sync_outputs(Params& P, Cohort& C, bool with_viterbi) {
   P.path.resize((size_t)P.n_ind * P.n_sites, 0);
   // indF / alpha are the cohort's on every handle; the frequencies those of its own sites
@@ -1361,9 +1431,10 @@ void parse_cmd_args(Params& P, int argc, char** argv) {  // parse_args.cpp:41-22
       {"ibd_bed", no_argument, nullptr, 1010},        {"ind_names", required_argument, nullptr, 1011},
       {"sample_paths", required_argument, nullptr, 1012}, {"sample_seed", required_argument, nullptr, 1013},
       {"sample_keep", required_argument, nullptr, 1014},
+      {"indF_se", no_argument, nullptr, 1015},        {"se_kat", no_argument, nullptr, 1016},
       {0, 0, 0, 0}};
   long taus_kat = 0;
-  bool parse_kat = false;
+  bool parse_kat = false, se_kat = false;
   P.seed = rand() % 1000;  // parse_args.cpp:30 (unseeded rand(): a constant)
   int c;
   while ((c = getopt_long_only(argc, argv, "g:Z:lLn:s:Gf:F:e:i:IAo:X:b:m:M:E:x:V:S:", long_options,
@@ -1398,6 +1469,8 @@ void parse_cmd_args(Params& P, int argc, char** argv) {  // parse_args.cpp:41-22
       case 1012: P.sample_paths = (unsigned)atoi(optarg); break;
       case 1013: P.sample_seed = strtoull(optarg, nullptr, 10); break;
       case 1014: P.sample_keep = (unsigned)atoi(optarg); break;
+      case 1015: P.indF_se = true; break;
+      case 1016: se_kat = true; break;
       case 1000:
         if (!strcmp(optarg, "exact")) P.mode = NGHMM_MODE_EXACT;
         else if (!strcmp(optarg, "fast")) P.mode = NGHMM_MODE_FAST;
@@ -1438,6 +1511,16 @@ void parse_cmd_args(Params& P, int argc, char** argv) {  // parse_args.cpp:41-22
     printf("parse_kat ok %lu tokens %lu lines\n", n_tok, n_line);
     exit(0);
   }
+  if (se_kat) {  // the standard-error rule on standard input: lines "indF alpha h_FF h_FA h_AA"
+    double v[5];
+    while (scanf("%lf %lf %lf %lf %lf", &v[0], &v[1], &v[2], &v[3], &v[4]) == 5) {
+      const SeOut se = se_rule(v[0], v[1], v[2], v[3], v[4]);
+      put_g(stdout, se.se_F, '\t');
+      put_g(stdout, se.se_A, '\t');
+      put_g(stdout, se.corr, '\n');
+    }
+    exit(0);
+  }
   if (taus_kat > 0) {  // known-answer check of the generator: the N-th raw output for --seed
     Taus rng(P.seed);
     uint32_t v = 0;
@@ -1476,6 +1559,8 @@ void parse_cmd_args(Params& P, int argc, char** argv) {  // parse_args.cpp:41-22
     fatal(__FUNCTION__, "--sample_keep is larger than --sample_paths!");
   if (P.sample_paths && !nghmm_chain_sample_paths)
     fatal(__FUNCTION__, "--sample_paths: the library has no nghmm_chain_sample_paths!");
+  if (P.indF_se && !nghmm_chain_obs_info)
+    fatal(__FUNCTION__, "--indF_se: the library has no nghmm_chain_obs_info!");
   if (P.min_iters < 1 || P.max_iters < 1 || P.min_iters >= P.max_iters)
     fatal(__FUNCTION__, "invalid number of iterations!");
   if (P.n_threads < 1) fatal(__FUNCTION__, "invalid number of threads!");
@@ -1507,7 +1592,8 @@ void parse_cmd_args(Params& P, int argc, char** argv) {  // parse_args.cpp:41-22
     gzclose(fh);
     if (P.ind_names.size() != P.n_ind)
       fatal(__FUNCTION__, "number of lines in --ind_names file is not --n_ind!");
-    if (!P.ibd_bed && !P.sample_paths) warn(__FUNCTION__, "--ind_names is only used by --ibd_bed and --sample_paths");
+    if (!P.ibd_bed && !P.sample_paths && !P.indF_se)
+      warn(__FUNCTION__, "--ind_names is only used by --ibd_bed, --sample_paths and --indF_se");
   }
   P.prefix = P.out_prefix;
 }
@@ -1601,6 +1687,7 @@ void finish_run(Params& P, Cohort& C) {
   }
   print_iter(P, C);
   if (P.sample_paths) write_samples(P, C);
+  if (P.indF_se) write_indF_se(P, C);
   if (P.verbose >= 2)  // (not a line of the reference's)
     fprintf(P.out, "> decoded in %.2f s, output files written in %.2f s\n", t1 - t0, omp_get_wtime() - t1);
 }
@@ -1713,6 +1800,7 @@ int main(int argc, char** argv) {
     for (unsigned r = 0; r < R; r++) {
       if (r == best || P.keep_starts) {
         if (r == best && !P.keep_starts) runs[r].prefix = P.out_prefix;
+        runs[r].indF_se = P.indF_se && r == best;   // the winning replicate's only
         finish_run(runs[r], cs[r]);
       }
       fclose(runs[r].out);
@@ -1724,6 +1812,7 @@ int main(int argc, char** argv) {
       std::vector<std::string> exts = {".indF", ".ibd", ".geno"};
       if (P.ibd_bed) exts.push_back(".ibd.bed");
       if (P.sample_paths) exts.push_back(".ibd.samples");
+      if (P.indF_se) exts.push_back(".indF.se");
       for (unsigned k = 1; P.sample_paths && k <= P.sample_keep; k++) {
         char tag[32];
         snprintf(tag, sizeof tag, ".sample_%02u.ibd", k);

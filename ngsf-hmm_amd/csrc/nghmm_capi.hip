@@ -565,7 +565,7 @@ int nghmm_destroy(nghmm_t* h) {
                  h->d_alpha, h->d_ind_lkl, h->d_flags, h->d_pt_ind, h->d_pt_F, h->d_pt_A,
                  h->d_pt_lkl, h->d_bp, h->d_path_sites, h->d_path, h->d_tmp, h->d_passes, h->d_vit,
                  h->d_gl_shard, h->d_geno, h->d_text, h->d_codes_shard, h->d_uniform, h->d_stage,
-                 h->d_freq_new, h->d_hap, h->d_tseg, h->d_trec, h->d_samp,
+                 h->d_freq_new, h->d_hap, h->d_tseg, h->d_trec, h->d_samp, h->d_info,
                  h->d_stage8, h->g_send, h->g_recv, h->g_freq_own, h->g_freq_all};
   if (h->g_xstream) (void)hipStreamDestroy(h->g_xstream);
   if (h->d_flags_bg) (void)hipFree(h->d_flags_bg);

@@ -146,6 +146,8 @@ def load_library():
         "nghmm_sample_paths": (i32, [vp, u64, u32, vp, u32, C.POINTER(C.c_uint8)]),
         "nghmm_chain_sample_paths": (i32, [C.POINTER(vp), i32, u64, u32, vp, u32,
                                            C.POINTER(C.c_uint8)]),
+        "nghmm_obs_info": (i32, [vp, dp, dp, vp]),
+        "nghmm_chain_obs_info": (i32, [C.POINTER(vp), i32, dp, dp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -183,6 +185,7 @@ EXPORTED_SYMBOLS = [
     "nghmm_chain_viterbi", "nghmm_alloc_host", "nghmm_free_host",
     "nghmm_ibd_tracts", "nghmm_chain_ibd_tracts",
     "nghmm_sample_paths", "nghmm_chain_sample_paths",
+    "nghmm_obs_info", "nghmm_chain_obs_info",
 ]
 
 OBJECTIVE_FN = C.CFUNCTYPE(C.c_double, C.c_uint32, C.c_double, C.c_double, C.c_void_p)
@@ -287,6 +290,59 @@ def path_stats_summary(stats, q=(0.025, 0.5, 0.975)):
     """Per-individual quantiles over the draws of every field of sample_paths' records:
     {field: array [len(q)][I]}."""
     return {f: np.quantile(stats[f].astype(np.float64), q, axis=0) for f in PATH_STATS_DTYPE.names}
+
+
+# nghmm_info (include/nghmm.h): one record per individual of obs_info
+INFO_DTYPE = np.dtype([("lkl", np.float64), ("g_F", np.float64), ("g_A", np.float64),
+                       ("h_FF", np.float64), ("h_FA", np.float64), ("h_AA", np.float64)])
+
+
+def _obs_info(call, check, n_ind, indF, alpha):
+    if (indF is None) != (alpha is None):
+        raise NgsFHMMError(-10, "obs_info: indF and alpha are given both or neither")
+    out = np.zeros(n_ind, dtype=INFO_DTYPE)
+    if indF is None:
+        check(call(None, None, C.c_void_p(out.ctypes.data)))
+        return out
+    F = np.ascontiguousarray(np.broadcast_to(np.asarray(indF, dtype=np.float64), (n_ind,)))
+    A = np.ascontiguousarray(np.broadcast_to(np.asarray(alpha, dtype=np.float64), (n_ind,)))
+    check(call(_dp(F), _dp(A), C.c_void_p(out.ctypes.data)))
+    return out
+
+
+def std_errors(info, indF, alpha):
+    """Standard errors of indF and alpha and their correlation from obs_info's records taken AT
+    the estimates (indF, alpha): (se_indF, se_alpha, corr), one value per individual.  They are
+    conditional on the allele frequencies, which obs_info holds fixed.  The rule (the host's
+    --indF_se applies the same one):
+
+    * A parameter on its bound is treated as fixed: its se is NaN and it leaves the inversion.
+      On its bound: indF < 1e-5 or indF > 1 - 1e-5 (the .indF file's NA rule, EM.cpp:293-310);
+      alpha <= 1e-15 or alpha >= 10 (the optimizer's box).
+    * indF on its bound makes all three NaN: alpha is then unidentified, which is why the
+      reference prints NA for it.
+    * A free block of -h (the observed information) that is not positive definite gives NaN for
+      that block: both free, -h_FF > 0 and det(-h) > 0 are needed; alpha on its bound, -h_FF > 0.
+    * Otherwise se = sqrt of the diagonal of (-h)^-1 over the free parameters, corr its
+      off-diagonal over the product of the two se (NaN unless both are free)."""
+    F = np.broadcast_to(np.asarray(indF, dtype=np.float64), info.shape)
+    A = np.broadcast_to(np.asarray(alpha, dtype=np.float64), info.shape)
+    n = len(info)
+    se_F, se_A, corr = (np.full(n, np.nan) for _ in range(3))
+    for i in range(n):
+        if F[i] < 1e-5 or F[i] > 1 - 1e-5:
+            continue
+        a, b, d = -info["h_FF"][i], -info["h_FA"][i], -info["h_AA"][i]
+        if A[i] <= 1e-15 or A[i] >= 10.0:
+            if a > 0:
+                se_F[i] = math.sqrt(1.0 / a)
+            continue
+        det = a * d - b * b
+        if a > 0 and det > 0:
+            se_F[i] = math.sqrt(d / det)
+            se_A[i] = math.sqrt(a / det)
+            corr[i] = -b / math.sqrt(a * d)
+    return se_F, se_A, corr
 
 
 KERNEL_SLOTS = {"emission": 0, "forward": 1, "backward": 2, "lkl_batch": 3, "est_maf": 4,
@@ -668,6 +724,15 @@ class NgsFHMM:
         return _sample_paths(lambda *a: self.lib.nghmm_sample_paths(self._h, *a), self._check,
                              self.n_ind, self.n_sites, n_draws, seed, keep)
 
+    def obs_info(self, indF=None, alpha=None):
+        """Per individual the log-likelihood, its gradient and its Hessian in (indF, alpha) under
+        the current emissions, from exact derivatives (nghmm_obs_info): a structured array [I] of
+        INFO_DTYPE.  indF / alpha: the points ([I] or a scalar each); neither: the current
+        parameters.  The allele frequencies are held fixed; std_errors turns the records into
+        standard errors."""
+        return _obs_info(lambda *a: self.lib.nghmm_obs_info(self._h, *a), self._check, self.n_ind,
+                         indF, alpha)
+
     # -- measurement -------------------------------------------------------
     def kernel_ms(self, name):
         """(milliseconds, launches) of a kernel family in the last call that ran it.  Fast mode's
@@ -793,6 +858,12 @@ class Chain:
         return _sample_paths(
             lambda *a: self.lib.nghmm_chain_sample_paths(self._arr, len(self.handles), *a),
             self.handles[0]._check, self.n_ind, self.n_sites, n_draws, seed, keep)
+
+    def obs_info(self, indF=None, alpha=None):
+        """NgsFHMM.obs_info over the chain (nghmm_chain_obs_info)."""
+        self._members_open()
+        return _obs_info(lambda *a: self.lib.nghmm_chain_obs_info(self._arr, len(self.handles), *a),
+                         self.handles[0]._check, self.n_ind, indF, alpha)
 
     @property
     def freq(self):
