@@ -42,9 +42,9 @@ int info_impl(nghmm_t** hs, int n, const double* F, const double* alpha, nghmm_i
     nghmm_t* h = hs[r];
     if ((rc = use_device(h))) return rc;
     const uint32_t C = fast ? h->fast.C : 0;
-    if ((rc = grow(&h->d_info, &h->info_cap, (2 * I + info_scratch_doubles(I, C)) * sizeof(double))))
+    if ((rc = h->d_info.reserve((2 * I + info_scratch_doubles(I, C)) * sizeof(double))))
       return rc;
-    double* d_F = reinterpret_cast<double*>(h->d_info);
+    double* d_F = reinterpret_cast<double*>(h->d_info.p);
     double* d_A = d_F + I;
     double* d_part = d_A + I;
     double* d_out = d_part + I * (uint64_t)(C ? C : 1) * kJetDoubles;

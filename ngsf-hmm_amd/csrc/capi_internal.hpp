@@ -24,6 +24,7 @@
 #include "../../include/nghmm.h"
 #include "../../include/nghmm_debug.h"
 #include "bfgs_batch.hpp"
+#include "capi_owners.hpp"
 #include "kernels.hpp"
 #include "kernels_fast.hpp"
 
@@ -33,7 +34,6 @@ namespace capi {
 
 // the message of the last failing call on this thread (include/nghmm.h, nghmm_last_error)
 extern thread_local std::string g_last_error;
-void set_error(const char* fmt, ...);
 
 #define HIP_TRY(expr)                                                              \
   do {                                                                             \
@@ -53,87 +53,83 @@ enum Slot { SLOT_EMISSION = 0, SLOT_FORWARD = 1, SLOT_BACKWARD = 2, SLOT_LKL = 3
 using namespace capi;
 
 struct ChainCtx;   // nghmm_chain_setup
+// Everything the handle takes from the runtime is a member that releases itself
+// (capi_owners.hpp).  Members go in reverse order of declaration, after the destructor has
+// drained the streams: so the streams and the handle's events come first here -- they go last,
+// after every buffer -- and the lanes hold their events before their buffers.
 struct nghmm_handle {
+  ~nghmm_handle();   // nghmm_capi.hip
   uint64_t I = 0, S = 0;
   int device = 0, mode = NGHMM_MODE_EXACT;
-  hipStream_t stream = nullptr;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr, ev_sync = nullptr;
+  Stream stream;
+  Event ev0, ev1, ev_sync;
+  // exact mode, fused iteration: est_maf on a second stream underneath the objective rounds
+  Stream aux_stream;
+  Stream g_xstream;   // member of a group (below): the peer copies' stream
+  Event aux_ev0, aux_ev1, aux_go, aux_done;
+  static constexpr uint32_t kAuxPieces = 16;   // exact mode: est_maf underneath the rounds, in pieces
+  Event aux_piece_ev[kAuxPieces];
+  Event aux_estep_ev[3];                       // ... the E-step next to the first rounds: its timing
+  DevBuf<double> d_aux_params;                 // ... and its own copies of indF / alpha [2][I]
   // pinned landing places of what every call reads back -- the error flags, and a fused iteration's
   // log-likelihoods: a copy to pageable memory is staged and waited for by the runtime, one each
-  int* h_flags_pin = nullptr;      // [NFLAGS]
-  double* h_lkl_pin = nullptr;     // [I]
-  // exact mode, fused iteration: est_maf on a second stream underneath the objective rounds
-  hipStream_t aux_stream = nullptr;
-  hipEvent_t aux_ev0 = nullptr, aux_ev1 = nullptr, aux_go = nullptr, aux_done = nullptr;
-  static constexpr uint32_t kAuxPieces = 16;   // exact mode: est_maf underneath the rounds, in pieces
-  hipEvent_t aux_piece_ev[kAuxPieces] = {};
-  hipEvent_t aux_estep_ev[3] = {};             // ... the E-step next to the first rounds: its timing
-  double* d_aux_params = nullptr;              // ... and its own copies of indF / alpha [2][I]
+  PinBuf<int> h_flags_pin;         // [NFLAGS]
+  PinBuf<double> h_lkl_pin;        // [I]
   hipEvent_t param_snapshot_ev = nullptr;      // (borrowed) those copies are made: an M-step's new parameters wait for it
   bool blocking_sync = false;
   bool loaded = false;
   bool warmed = false;   // nghmm_emission has set up what the first EM iteration needs
 
-  double *d_gl = nullptr, *d_pos = nullptr, *d_freq = nullptr, *d_eprob = nullptr, *d_fw = nullptr,
-         *d_marg = nullptr, *d_indF = nullptr, *d_alpha = nullptr, *d_ind_lkl = nullptr;
-  int* d_flags = nullptr;
+  DevBuf<double> d_gl, d_pos;   // (a replica borrows its parent's: nghmm_create_replica)
+  DevBuf<double> d_freq, d_eprob, d_fw, d_marg, d_indF, d_alpha, d_ind_lkl;
+  DevBuf<int> d_flags;
 
-  uint32_t* d_pt_ind = nullptr;
-  double *d_pt_F = nullptr, *d_pt_A = nullptr, *d_pt_lkl = nullptr;
-  size_t pt_cap = 0;
+  // the objective points of one round: the four grow together (ensure_points)
+  DevScratch<uint32_t> d_pt_ind;
+  DevScratch<double> d_pt_F, d_pt_A, d_pt_lkl;
 
-  uint8_t *d_bp = nullptr, *d_path_sites = nullptr, *d_path = nullptr;
-  double* d_vit = nullptr;  // Viterbi scratch: transition logs of one site chunk + carry state
-  double* d_tmp = nullptr;  // S*I*2 doubles, transposes for host read-back
-  double* d_geno = nullptr;  // .geno posteriors of one site chunk
-  size_t geno_cap = 0;
-  char* d_text = nullptr;    // formatted posterior lines of one batch of individuals
-  size_t text_cap = 0;
+  DevBuf<uint8_t> d_bp, d_path_sites, d_path;
+  DevBuf<double> d_vit;  // Viterbi scratch: transition logs of one site chunk + carry state
+  DevBuf<double> d_tmp;  // S*I*2 doubles, transposes for host read-back
+  DevScratch<double> d_geno;  // .geno posteriors of one site chunk
+  DevScratch<char> d_text;    // formatted posterior lines of one batch of individuals
   bool tmp_is_posteriors = false;  // d_tmp holds the [I][S] posteriors of the last E-step
   // d_path_sites holds a decoded path of the loaded data (nghmm_geno_posteriors allocates and
   // zeroes it before any decode)
   bool path_decoded = false;
   // IBD tracts (capi_tracts.hip): per (individual, segment) counts / offsets, carried sums, the
   // chromosome-start mask and scan scratch; the records (raw, then compacted) and their offsets
-  uint8_t* d_tseg = nullptr;
-  size_t tseg_cap = 0;
-  uint8_t* d_trec = nullptr;
-  size_t trec_cap = 0;
+  DevScratch<uint8_t> d_tseg, d_trec;
   // sampled paths (capi_sample.hip): maps, lane-chunk statistics, kept paths of one batch of draws
-  uint8_t* d_samp = nullptr;
-  size_t samp_cap = 0;
+  DevScratch<uint8_t> d_samp;
   // observed information (capi_info.hip): the points, the waves' jets, the records
-  uint8_t* d_info = nullptr;
-  size_t info_cap = 0;
-  uint32_t* d_passes = nullptr;
-  double *d_freq_new = nullptr, *d_hap = nullptr;  // --freq_est 2 as intended: [S], [S][4]
+  DevScratch<uint8_t> d_info;
+  DevBuf<double> d_freq_new, d_hap;  // --freq_est 2 as intended: [S], [S][4]
 
   // multi-GPU shard
   uint64_t I_tot = 0, ind_begin = 0, site_begin = 0, S_own = 0;
-  double* d_gl_shard = nullptr;
+  DevBuf<double> d_gl_shard;
 
   // packed handle (NGHMM_GENO_PACKED): called genotypes as 2-bit codes (glview.hpp); d_gl
   // does not exist
   bool packed = false;
-  uint32_t* d_codes = nullptr;        // [S][I] cells, 16 per word
-  uint32_t* d_codes_shard = nullptr;  // [S_own][I_tot] cells of the frequency step's site range
-  double* d_cls_log = nullptr;        // [4][3] prepared log likelihoods of the four classes
+  DevBuf<uint32_t> d_codes;           // [S][I] cells, 16 per word (a replica borrows its parent's)
+  DevBuf<uint32_t> d_codes_shard;     // [S_own][I_tot] cells of the frequency step's site range
+  DevBuf<double> d_cls_log;           // [4][3] prepared log likelihoods of the four classes (borrowed likewise)
   double h_cls_proto[12] = {0};       // ... as nghmm_create prepared them (row 3: the reader's
                                       // missing genotype); a load starts from these
-  unsigned long long* d_uniform = nullptr;  // the one value every uniform cell carries (~0: none yet)
+  DevBuf<unsigned long long> d_uniform;     // the one value every uniform cell carries (~0: none yet)
   // chunked loading (nghmm_load_begin .. nghmm_load_end)
   uint64_t lkl_redone = 0;            // objective points re-evaluated by the general kernel
   // fast-mode M-step after its first round: the individuals in two halves, each with its own
   // buffers and events, so that the host advances one half's optimizers while the GPU
   // evaluates the other half's points (mstep_indf_impl)
   struct LklAsync {
-    double* d_lkl = nullptr;   // device results
-    size_t cap = 0;
-    double* h_lkl = nullptr;   // pinned host results
-    size_t h_cap = 0;
-    int* d_flags = nullptr;
-    int* h_flags = nullptr;    // pinned
-    hipEvent_t ev0 = nullptr, ev1 = nullptr, ev_done = nullptr;
+    Event ev0, ev1, ev_done;
+    DevScratch<double> d_lkl;   // device results
+    PinScratch<double> h_lkl;   // pinned host results
+    DevBuf<int> d_flags;
+    PinBuf<int> h_flags;
     std::vector<uint32_t> ind;
     std::vector<double> F, A;
     uint64_t lo = 0, hi = 0;
@@ -145,10 +141,10 @@ struct nghmm_handle {
   // digests that round's values.  Error flags of their own (the rounds clear theirs), a pool
   // of timing events (one pair per piece, read when the iteration ends).
   struct BgSpan {
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    Event ev0, ev1;
     int slot = 0;
   };
-  int* d_flags_bg = nullptr;
+  DevBuf<int> d_flags_bg;
   bool flags_bg_clear = false;   // the last iteration's epilogue kernel left d_flags_bg zeroed
   std::vector<BgSpan> bg_spans;
   size_t bg_used = 0;
@@ -159,20 +155,17 @@ struct nghmm_handle {
   // member of a group (nghmm_group_setup): exchange buffers on this handle's device and a
   // second stream for the peer copies, which run under the remaining objective rounds
   int g_n = 0, g_rank = 0;
-  double *g_send = nullptr, *g_recv = nullptr, *g_freq_own = nullptr, *g_freq_all = nullptr;
-  hipStream_t g_xstream = nullptr;
+  DevBuf<double> g_send, g_recv, g_freq_own, g_freq_all;
   // member of an in-process chain of site shards (nghmm_chain_setup): the exchange buffers of
   // fast.shard on this handle's device and the chain's shared state
   struct ChainCtx* chain = nullptr;
-  double *c_send = nullptr, *c_recv = nullptr;
+  DevBuf<double> c_send, c_recv;   // (chain_release gives them back when the chain dissolves)
   bool loading = false;
   // sites that have arrived since nghmm_load_begin, as disjoint [begin, end) runs: every site
   // must arrive exactly once (a repeated site would OR two codes into a packed cell)
   std::map<uint64_t, uint64_t> load_cover;
-  double* d_stage = nullptr;          // staging buffer of one chunk of raw likelihoods
-  size_t stage_cap = 0;
-  int8_t* d_stage8 = nullptr;         // ... of one chunk of reader genotypes
-  size_t stage8_cap = 0;
+  DevScratch<double> d_stage;         // staging buffer of one chunk of raw likelihoods
+  DevScratch<int8_t> d_stage8;        // ... of one chunk of reader genotypes
 
   FastState fast;  // fast-mode layouts (kernels_fast.hip)
   BfgsBatch batch;  // one L-BFGS-B state machine per individual, storage reused across M-steps
@@ -227,28 +220,5 @@ int tracts_to_host(nghmm_t* h, int source, double threshold, uint64_t min_sites,
                    std::vector<nghmm_tract>& out);
 // source / threshold of nghmm_ibd_tracts; sets the error message
 int tracts_check_args(nghmm_t* h, int source, double threshold, const char* who);
-
-template <typename T>
-int dev_alloc(T** p, size_t n) {
-  if (n == 0) n = 1;
-  hipError_t e = hipMalloc((void**)p, n * sizeof(T));
-  if (e != hipSuccess) {
-    set_error("hipMalloc of %zu bytes failed: %s", n * sizeof(T), hipGetErrorString(e));
-    return NGHMM_ERR_NOMEM;
-  }
-  return NGHMM_OK;
-}
-
-// a scratch buffer of the handle that grows on demand (its contents are not kept)
-inline int grow(uint8_t** p, size_t* cap, size_t bytes) {
-  if (bytes <= *cap) return NGHMM_OK;
-  if (*p) (void)hipFree(*p);
-  *p = nullptr;
-  *cap = 0;
-  int rc;
-  if ((rc = dev_alloc(p, bytes))) return rc;
-  *cap = bytes;
-  return NGHMM_OK;
-}
 
 }  // namespace capi

@@ -29,28 +29,6 @@ static int after_gl_load(nghmm_t* h) {
   return NGHMM_OK;
 }
 
-static int ensure_stage(nghmm_t* h, size_t doubles) {
-  if (doubles <= h->stage_cap) return NGHMM_OK;
-  if (h->d_stage) (void)hipFree(h->d_stage);
-  h->d_stage = nullptr;
-  h->stage_cap = 0;
-  int rc;
-  if ((rc = dev_alloc(&h->d_stage, doubles))) return rc;
-  h->stage_cap = doubles;
-  return NGHMM_OK;
-}
-
-static int ensure_stage8(nghmm_t* h, size_t bytes) {
-  if (bytes <= h->stage8_cap) return NGHMM_OK;
-  if (h->d_stage8) (void)hipFree(h->d_stage8);
-  h->d_stage8 = nullptr;
-  h->stage8_cap = 0;
-  int rc;
-  if ((rc = dev_alloc(&h->d_stage8, bytes))) return rc;
-  h->stage8_cap = bytes;
-  return NGHMM_OK;
-}
-
 // flags a chunk loader looks at after its kernels
 static int check_load_flags(nghmm_t* h, bool check_nan) {
   int f[NFLAGS];
@@ -91,7 +69,7 @@ static int ingest_chunk(nghmm_t* h, uint64_t site_begin, uint64_t n_sites, const
     const double* cells = d_src;
     if (prepare) {
       if (!src_is_scratch) {  // never modify the caller's buffer
-        if ((rc = ensure_stage(h, n_cells * 3))) return rc;
+        if ((rc = h->d_stage.reserve(n_cells * 3))) return rc;
         HIP_TRY(hipMemcpyAsync(h->d_stage, d_src, n_cells * 3 * sizeof(double),
                                hipMemcpyDeviceToDevice, h->stream));
         cells = h->d_stage;
@@ -233,7 +211,7 @@ static int load_sites_impl(nghmm_t* h, uint64_t site_begin, uint64_t n_sites, co
   }
   double* dst = h->packed ? nullptr : h->d_gl + site_begin * h->I * 3;
   if (h->packed) {
-    if ((rc = ensure_stage(h, n_cells * 3))) return fail_load(h, rc);
+    if ((rc = h->d_stage.reserve(n_cells * 3))) return fail_load(h, rc);
     dst = h->d_stage;
   }
   if (hipMemcpyAsync(dst, src, n_cells * 3 * sizeof(double), hipMemcpyHostToDevice, h->stream) !=
@@ -271,7 +249,7 @@ int nghmm_load_geno_sites(nghmm_t* h, uint64_t site_begin, uint64_t n_sites, con
   auto body = [&]() -> int {
     const uint64_t n_cells = n_sites * h->I, cell0 = site_begin * h->I;
     int rc;
-    if ((rc = ensure_stage8(h, n_cells))) return rc;
+    if ((rc = h->d_stage8.reserve(n_cells))) return rc;
     HIP_TRY(hipMemcpyAsync(h->d_stage8, geno, n_cells, hipMemcpyHostToDevice, h->stream));
     if ((rc = clear_flags(h))) return rc;
     if (h->packed) {
@@ -363,7 +341,7 @@ int nghmm_get_gl(nghmm_t* h, double* gl) {
   const size_t cells = (size_t)h->I * h->S;
   const double* src = h->d_gl;
   if (h->packed) {  // test / debug aid: unpack through the staging buffer
-    if ((rc = ensure_stage(h, cells * 3))) return rc;
+    if ((rc = h->d_stage.reserve(cells * 3))) return rc;
     launch_unpack_cells(h->stream, own_gl(h), cells, h->d_stage);
     HIP_TRY(hipGetLastError());
     src = h->d_stage;

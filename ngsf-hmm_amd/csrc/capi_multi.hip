@@ -78,9 +78,9 @@ int nghmm_viterbi_shard_forward(nghmm_t* h, const double* scores_in, double* sco
   int rc;
   if ((rc = use_device(h))) return rc;
   const size_t blocked = viterbi_blocked_bytes(h->S, h->I);
-  if (!h->d_bp && (rc = dev_alloc(&h->d_bp, blocked + h->I))) return rc;
-  if (!h->d_path_sites && (rc = dev_alloc(&h->d_path_sites, blocked))) return rc;
-  if (!h->d_path && (rc = dev_alloc(&h->d_path, (size_t)h->I * h->S))) return rc;
+  if (!h->d_bp && (rc = h->d_bp.alloc(blocked + h->I))) return rc;
+  if (!h->d_path_sites && (rc = h->d_path_sites.alloc(blocked))) return rc;
+  if (!h->d_path && (rc = h->d_path.alloc((size_t)h->I * h->S))) return rc;
   uint64_t chunk;
   double* d_state;
   if ((rc = viterbi_scratch(h, &chunk, &d_state))) return rc;
@@ -109,18 +109,14 @@ int nghmm_viterbi_shard_back(nghmm_t* h, const uint8_t* state_after, uint8_t* st
   uint8_t* d_last = h->d_bp + viterbi_blocked_bytes(h->S, h->I);
   if (state_after)  // else: the last range, whose forward half left the arg max there
     HIP_TRY(hipMemcpyAsync(d_last, state_after, h->I, hipMemcpyHostToDevice, h->stream));
-  uint8_t* d_before = nullptr;
-  if ((rc = dev_alloc(&d_before, (size_t)h->I))) return rc;
+  DevBuf<uint8_t> d_before;
+  if ((rc = d_before.alloc(h->I))) return rc;
   launch_viterbi_back_exact(h->stream, h->d_bp, h->S, h->I, h->d_path_sites, d_before);
   launch_unblock_path(h->stream, h->d_path_sites, h->S, h->I, h->d_path);
-  hipError_t e = hipGetLastError();
-  if (e == hipSuccess)
-    e = hipMemcpyAsync(state_before, d_before, h->I, hipMemcpyDeviceToHost, h->stream);
-  if (e == hipSuccess)
-    e = hipMemcpyAsync(path, h->d_path, (size_t)h->I * h->S, hipMemcpyDeviceToHost, h->stream);
-  if (e == hipSuccess) e = sync_stream(h);
-  (void)hipFree(d_before);
-  HIP_TRY(e);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(state_before, d_before, h->I, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipMemcpyAsync(path, h->d_path, (size_t)h->I * h->S, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(sync_stream(h));
   h->path_decoded = true;
   return NGHMM_OK;
 }
@@ -135,9 +131,7 @@ int nghmm_load_gl_site_shard(nghmm_t* h, const double* gl_site_shard) {
   int rc;
   if ((rc = use_device(h))) return rc;
   const size_t n = (size_t)h->S_own * h->I_tot * 3;
-  if (h->d_gl_shard) (void)hipFree(h->d_gl_shard);
-  h->d_gl_shard = nullptr;
-  if ((rc = dev_alloc(&h->d_gl_shard, n))) return rc;
+  if ((rc = h->d_gl_shard.alloc(n))) return rc;   // (the old copy goes first)
   HIP_TRY(hipMemcpyAsync(h->d_gl_shard, gl_site_shard, n * sizeof(double), hipMemcpyHostToDevice,
                          h->stream));
   if (h->mode == NGHMM_MODE_FAST) fast_exp(h->stream, h->d_gl_shard, h->d_gl_shard, n);
@@ -163,9 +157,7 @@ int nghmm_load_geno_site_shard_dev(nghmm_t* h, const uint8_t* d_codes_bytes) {
   int rc;
   if ((rc = use_device(h))) return rc;
   const size_t n = (size_t)h->S_own * h->I_tot;
-  if (h->d_codes_shard) (void)hipFree(h->d_codes_shard);
-  h->d_codes_shard = nullptr;
-  if ((rc = dev_alloc(&h->d_codes_shard, n / 16 + 2))) return rc;
+  if ((rc = h->d_codes_shard.alloc(n / 16 + 2))) return rc;   // (the old copy goes first)
   HIP_TRY(hipDeviceSynchronize());  // the caller's buffer: written on a stream of its own (capi_load.hip)
   launch_bytes_to_codes(h->stream, d_codes_bytes, n, h->d_codes_shard);
   HIP_TRY(hipGetLastError());
@@ -183,9 +175,7 @@ int nghmm_load_gl_site_shard_dev(nghmm_t* h, const double* d_gl_site_shard) {
   int rc;
   if ((rc = use_device(h))) return rc;
   const size_t n = (size_t)h->S_own * h->I_tot * 3;
-  if (h->d_gl_shard) (void)hipFree(h->d_gl_shard);
-  h->d_gl_shard = nullptr;
-  if ((rc = dev_alloc(&h->d_gl_shard, n))) return rc;
+  if ((rc = h->d_gl_shard.alloc(n))) return rc;   // (the old copy goes first)
   HIP_TRY(hipDeviceSynchronize());  // the caller's buffer: written on a stream of its own (capi_load.hip)
   HIP_TRY(hipMemcpyAsync(h->d_gl_shard, d_gl_site_shard, n * sizeof(double),
                          hipMemcpyDeviceToDevice, h->stream));
@@ -217,7 +207,7 @@ int nghmm_pack_posteriors_dev(nghmm_t* h, uint64_t site_lo, uint64_t site_hi, do
 
 int nghmm_mstep_freq_sites_dev(nghmm_t* h, const double* d_marg_blocks, double* d_freq_out) {
   g_last_error.clear();
-  if (!h || !d_marg_blocks || !d_freq_out || !(h->packed ? (void*)h->d_codes_shard : (void*)h->d_gl_shard))
+  if (!h || !d_marg_blocks || !d_freq_out || !(h->packed ? (void*)h->d_codes_shard.p : (void*)h->d_gl_shard.p))
     return NGHMM_ERR_ARG;
   int rc;
   if ((rc = use_device(h))) return rc;
@@ -365,15 +355,11 @@ int nghmm_group_setup(nghmm_t** hs, int n) {
     h->g_n = n;
     h->g_rank = r;
     if (n == 1) continue;
-    void* old[] = {h->g_send, h->g_recv, h->g_freq_own, h->g_freq_all};
-    for (void* p : old)
-      if (p) (void)hipFree(p);
-    h->g_send = h->g_recv = h->g_freq_own = h->g_freq_all = nullptr;
-    if ((rc = dev_alloc(&h->g_send, (size_t)S * I))) return rc;
-    if ((rc = dev_alloc(&h->g_recv, (size_t)S * I))) return rc;
-    if ((rc = dev_alloc(&h->g_freq_own, (size_t)S_own))) return rc;
-    if ((rc = dev_alloc(&h->g_freq_all, (size_t)S))) return rc;
-    if (!h->g_xstream) HIP_TRY(hipStreamCreateWithFlags(&h->g_xstream, hipStreamNonBlocking));
+    for (auto* b : {&h->g_send, &h->g_recv, &h->g_freq_own, &h->g_freq_all}) b->reset();  // an earlier group's
+    if ((rc = h->g_send.alloc((size_t)S * I)) || (rc = h->g_recv.alloc((size_t)S * I)) ||
+        (rc = h->g_freq_own.alloc(S_own)) || (rc = h->g_freq_all.alloc(S)))
+      return rc;
+    if (!h->g_xstream && (rc = h->g_xstream.create())) return rc;
   }
   if (n == 1) return NGHMM_OK;
   // static site-shard copies: rank r gets the likelihoods of ALL individuals for its site range,
@@ -383,9 +369,7 @@ int nghmm_group_setup(nghmm_t** hs, int n) {
     if ((rc = use_device(h))) return rc;
     const uint64_t lo = (uint64_t)r * S_own;
     if (!h->packed) {
-      if (h->d_gl_shard) (void)hipFree(h->d_gl_shard);
-      h->d_gl_shard = nullptr;
-      if ((rc = dev_alloc(&h->d_gl_shard, (size_t)S_own * I_tot * 3))) return rc;
+      if ((rc = h->d_gl_shard.alloc((size_t)S_own * I_tot * 3))) return rc;
       for (int q = 0; q < n; ++q)
         HIP_TRY(hipMemcpy2DAsync(h->d_gl_shard + (size_t)q * I * 3, I_tot * 3 * sizeof(double),
                                  hs[q]->d_gl + lo * I * 3, I * 3 * sizeof(double),
@@ -394,34 +378,19 @@ int nghmm_group_setup(nghmm_t** hs, int n) {
       HIP_TRY(hipGetLastError());
       HIP_TRY(sync_stream(h));
     } else {
-      uint8_t *bytes = nullptr, *part = nullptr;  // [S_own][I_tot] on r; [S_own][I] on q
-      if ((rc = dev_alloc(&bytes, (size_t)S_own * I_tot))) return rc;
-      for (int q = 0; q < n && rc == NGHMM_OK; ++q) {
-        hipError_t e = hipSetDevice(hs[q]->device);
-        if (e == hipSuccess) e = hipMalloc((void**)&part, (size_t)S_own * I);
-        if (e == hipSuccess) {
-          launch_codes_to_bytes(hs[q]->stream, hs[q]->d_codes, lo * I, S_own * I, part);
-          e = hipStreamSynchronize(hs[q]->stream);
-        }
-        if (e == hipSuccess) e = hipSetDevice(h->device);
-        if (e == hipSuccess)
-          e = hipMemcpy2DAsync(bytes + (size_t)q * I, I_tot, part, I, I, S_own,
-                               hipMemcpyDeviceToDevice, h->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-        if (part) {
-          (void)hipSetDevice(hs[q]->device);
-          (void)hipFree(part);
-          part = nullptr;
-          (void)hipSetDevice(h->device);
-        }
-        if (e != hipSuccess) {
-          set_error("nghmm_group_setup: %s", hipGetErrorString(e));
-          rc = NGHMM_ERR_HIP;
-        }
+      DevBuf<uint8_t> bytes;  // [S_own][I_tot] on r
+      if ((rc = bytes.alloc((size_t)S_own * I_tot))) return rc;
+      for (int q = 0; q < n; ++q) {
+        DevBuf<uint8_t> part;  // [S_own][I] on q
+        if ((rc = use_device(hs[q])) || (rc = part.alloc((size_t)S_own * I))) return rc;
+        launch_codes_to_bytes(hs[q]->stream, hs[q]->d_codes, lo * I, S_own * I, part);
+        HIP_TRY(hipStreamSynchronize(hs[q]->stream));
+        if ((rc = use_device(h))) return rc;
+        HIP_TRY(hipMemcpy2DAsync(bytes + (size_t)q * I, I_tot, part, I, I, S_own, hipMemcpyDeviceToDevice,
+                                 h->stream));
+        HIP_TRY(hipStreamSynchronize(h->stream));
       }
-      if (rc == NGHMM_OK) rc = nghmm_load_geno_site_shard_dev(h, bytes);
-      (void)hipFree(bytes);
-      if (rc != NGHMM_OK) return rc;
+      if ((rc = nghmm_load_geno_site_shard_dev(h, bytes))) return rc;
     }
   }
   return NGHMM_OK;
@@ -553,7 +522,7 @@ int chain_allgather(void* user, uint64_t n_bytes) {
   if (!cx->wait()) return 1;
   for (int q = 0; q < n && ok; ++q) {
     nghmm_t* o = cx->hs[q];
-    char* dst = reinterpret_cast<char*>(h->c_recv) + (size_t)q * n_bytes;
+    char* dst = reinterpret_cast<char*>(h->c_recv.p) + (size_t)q * n_bytes;
     const hipError_t e = o->device == h->device
                              ? hipMemcpyAsync(dst, o->c_send, n_bytes, hipMemcpyDeviceToDevice, h->stream)
                              : hipMemcpyPeerAsync(dst, h->device, o->c_send, o->device, n_bytes, h->stream);
@@ -594,9 +563,8 @@ void capi::chain_release(nghmm_t* h) {
     m->fast.shard.edges_from_round = false;
     (void)hipSetDevice(m->device);
     if (m->stream) (void)hipStreamSynchronize(m->stream);
-    if (m->c_send) (void)hipFree(m->c_send);
-    if (m->c_recv) (void)hipFree(m->c_recv);
-    m->c_send = m->c_recv = nullptr;
+    m->c_send.reset();
+    m->c_recv.reset();
   }
   if (dev_before >= 0) (void)hipSetDevice(dev_before);
   delete cx;
@@ -657,8 +625,8 @@ int nghmm_chain_setup(nghmm_t** hs, int n) {
   for (int r = 0; r < n; ++r) {
     nghmm_t* h = hs[r];
     const uint64_t bytes = nghmm_site_shard_bytes(h);
-    if ((rc = use_device(h)) || (rc = dev_alloc(&h->c_send, (size_t)(bytes / sizeof(double)))) ||
-        (rc = dev_alloc(&h->c_recv, (size_t)(bytes / sizeof(double)) * n)) ||
+    if ((rc = use_device(h)) || (rc = h->c_send.alloc(bytes / sizeof(double))) ||
+        (rc = h->c_recv.alloc(bytes / sizeof(double) * n)) ||
         (rc = nghmm_site_shard_setup(h, r, n, h->c_send, h->c_recv, bytes, chain_allgather, h))) {
       const std::string msg = g_last_error;
       for (int q = 0; q < n; ++q) chain_release(hs[q]);

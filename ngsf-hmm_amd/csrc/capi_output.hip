@@ -35,13 +35,7 @@ int nghmm_format_posteriors(nghmm_t* h, uint64_t ind_begin, uint64_t n_ind, char
   if ((rc = use_device(h))) return rc;
   if ((rc = posteriors_ind_major(h))) return rc;
   const size_t bytes = (size_t)n_ind * 9 * h->S;
-  if (bytes > h->text_cap) {
-    if (h->d_text) (void)hipFree(h->d_text);
-    h->d_text = nullptr;
-    h->text_cap = 0;
-    if ((rc = dev_alloc(&h->d_text, bytes))) return rc;
-    h->text_cap = bytes;
-  }
+  if ((rc = h->d_text.reserve(bytes))) return rc;
   if ((rc = clear_flags(h))) return rc;
   launch_format_fixed6(h->stream, h->d_tmp + ind_begin * h->S, n_ind, h->S, h->d_text, h->d_flags);
   HIP_TRY(hipGetLastError());
@@ -63,29 +57,17 @@ int nghmm_format_fixed6(nghmm_t* h, const double* values, uint64_t rows, uint64_
   int rc;
   if ((rc = use_device(h))) return rc;
   const size_t n = (size_t)rows * cols;
-  double* d_in = nullptr;
-  char* d_out = nullptr;
-  if ((rc = dev_alloc(&d_in, n))) return rc;
-  if ((rc = dev_alloc(&d_out, n * 9))) {
-    (void)hipFree(d_in);
-    return rc;
-  }
+  DevBuf<double> d_in;
+  DevBuf<char> d_out;
+  if ((rc = d_in.alloc(n)) || (rc = d_out.alloc(n * 9))) return rc;
   int bad = 0;
-  hipError_t e = hipMemcpyAsync(d_in, values, n * sizeof(double), hipMemcpyHostToDevice, h->stream);
-  if (e == hipSuccess) e = hipMemsetAsync(h->d_flags, 0, NFLAGS * sizeof(int), h->stream);
-  if (e == hipSuccess) {
-    launch_format_fixed6(h->stream, d_in, rows, cols, d_out, h->d_flags);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipMemcpyAsync(&bad, h->d_flags, sizeof bad, hipMemcpyDeviceToHost, h->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, n * 9, hipMemcpyDeviceToHost, h->stream);
-  if (e == hipSuccess) e = sync_stream(h);
-  (void)hipFree(d_in);
-  (void)hipFree(d_out);
-  if (e != hipSuccess) {
-    set_error("nghmm_format_fixed6: %s", hipGetErrorString(e));
-    return NGHMM_ERR_HIP;
-  }
+  HIP_TRY(hipMemcpyAsync(d_in, values, n * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  if ((rc = clear_flags(h))) return rc;
+  launch_format_fixed6(h->stream, d_in, rows, cols, d_out, h->d_flags);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(&bad, h->d_flags, sizeof bad, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipMemcpyAsync(out, d_out, n * 9, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(sync_stream(h));
   if (bad) {
     set_error("nghmm_format_fixed6: a value outside [0, 1]");
     return NGHMM_ERR_ARG;
@@ -102,17 +84,11 @@ int nghmm_geno_posteriors(nghmm_t* h, uint64_t site_begin, uint64_t n_sites, dou
     // not decoded yet: the reference's path[][] is still all zeros then (an intermediate
     // print_iter, EM.cpp:60-62)
     const size_t blocked = viterbi_blocked_bytes(h->S, h->I);
-    if ((rc = dev_alloc(&h->d_path_sites, blocked))) return rc;
+    if ((rc = h->d_path_sites.alloc(blocked))) return rc;
     HIP_TRY(hipMemsetAsync(h->d_path_sites, 0, blocked, h->stream));
   }
   const size_t n = (size_t)n_sites * h->I * 3;
-  if (n > h->geno_cap) {
-    if (h->d_geno) (void)hipFree(h->d_geno);
-    h->d_geno = nullptr;
-    h->geno_cap = 0;
-    if ((rc = dev_alloc(&h->d_geno, n))) return rc;
-    h->geno_cap = n;
-  }
+  if ((rc = h->d_geno.reserve(n))) return rc;
   launch_geno_post_exact(h->stream, own_gl(h), h->d_freq, h->d_path_sites, h->I, site_begin, n_sites,
                          h->d_geno);
   HIP_TRY(hipGetLastError());

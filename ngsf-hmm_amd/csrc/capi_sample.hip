@@ -60,9 +60,9 @@ int sample_impl(nghmm_t** hs, int n, uint64_t seed, uint32_t n_draws, nghmm_path
     if ((rc = use_device(h))) return rc;
     const uint64_t J = fast ? h->fast.J : 0, pitch = fast ? h->fast.Spad : h->S;
     const uint64_t body = sample_scratch_bytes(I, J, pitch, keep_batch);
-    if ((rc = grow(&h->d_samp, &h->samp_cap, body + I * 5 * sizeof(double)))) return rc;
+    if ((rc = h->d_samp.reserve(body + I * 5 * sizeof(double)))) return rc;
     x.scr = sample_scratch_carve(h->d_samp, I, J, pitch);
-    x.d_vin = reinterpret_cast<double*>(h->d_samp + body);
+    x.d_vin = reinterpret_cast<double*>(h->d_samp.p + body);
     x.d_vout = x.d_vin + I * 2;
     x.d_lkl = x.d_vout + I * 2;
     x.seg.resize((size_t)kSampleBatch * I);

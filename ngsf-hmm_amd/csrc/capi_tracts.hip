@@ -53,8 +53,8 @@ int tracts_device(nghmm_t* h, int source, double thr, uint64_t min_sites, const 
   const uint64_t S = h->S, I = h->I, nseg = tract_segments(S), nb = I * nseg, nblk = (S + 15) / 16;
   const uint64_t scr = tract_scan_scratch(nb);
   // d_tseg: offsets [nb + 1] | scan scratch | carried sums [nb] | chromosome-start mask [nblk]
-  if ((rc = grow(&h->d_tseg, &h->tseg_cap, (nb + 1 + scr) * 8 + nb * 8 + nblk * 4))) return rc;
-  uint64_t* off = reinterpret_cast<uint64_t*>(h->d_tseg);
+  if ((rc = h->d_tseg.reserve((nb + 1 + scr) * 8 + nb * 8 + nblk * 4))) return rc;
+  uint64_t* off = reinterpret_cast<uint64_t*>(h->d_tseg.p);
   uint64_t* scratch = off + nb + 1;
   double* carry = reinterpret_cast<double*>(scratch + scr);
   uint32_t* mask = reinterpret_cast<uint32_t*>(carry + nb);
@@ -70,8 +70,8 @@ int tracts_device(nghmm_t* h, int source, double thr, uint64_t min_sites, const 
   const bool filter = min_sites > 1;
   const uint64_t kscr = filter ? tract_scan_scratch(n) : 0;
   const size_t bytes = n * sizeof(TractRec) + (filter ? n * sizeof(TractRec) + (n + 1 + kscr) * 8 : 0);
-  if ((rc = grow(&h->d_trec, &h->trec_cap, bytes))) return rc;
-  TractRec* rec = reinterpret_cast<TractRec*>(h->d_trec);
+  if ((rc = h->d_trec.reserve(bytes))) return rc;
+  TractRec* rec = reinterpret_cast<TractRec*>(h->d_trec.p);
   *d_out = rec;
   *n_out = n;
   if (n == 0) return NGHMM_OK;

@@ -68,8 +68,8 @@ static int map_flags(const int* f);
 
 // Reads the kernel error flags and maps them to the reference's fatal errors.
 int check_flags(nghmm_t* h, const int* d_flags) {
-  if (!h->h_flags_pin)
-    HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&h->h_flags_pin), NFLAGS * sizeof(int), hipHostMallocDefault));
+  int rc;
+  if (!h->h_flags_pin && (rc = h->h_flags_pin.alloc(NFLAGS))) return rc;
   int* f = h->h_flags_pin;
   HIP_TRY(hipMemcpyAsync(f, d_flags ? d_flags : h->d_flags, NFLAGS * sizeof(int), hipMemcpyDeviceToHost,
                          h->stream));
@@ -98,22 +98,11 @@ static int map_flags(const int* f) {
 }
 
 int ensure_points(nghmm_t* h, size_t n) {
-  if (n <= h->pt_cap) return NGHMM_OK;
-  size_t cap = n + n / 4 + 1024;
-  if (h->d_pt_ind) (void)hipFree(h->d_pt_ind);
-  if (h->d_pt_F) (void)hipFree(h->d_pt_F);
-  if (h->d_pt_A) (void)hipFree(h->d_pt_A);
-  if (h->d_pt_lkl) (void)hipFree(h->d_pt_lkl);
-  h->d_pt_ind = nullptr;
-  h->d_pt_F = h->d_pt_A = h->d_pt_lkl = nullptr;
-  h->pt_cap = 0;
+  if (n <= h->d_pt_lkl.cap) return NGHMM_OK;  // (the last of the four to grow: the others hold as much)
+  const size_t cap = n + n / 4 + 1024;
   int rc;
-  if ((rc = dev_alloc(&h->d_pt_ind, cap))) return rc;
-  if ((rc = dev_alloc(&h->d_pt_F, cap))) return rc;
-  if ((rc = dev_alloc(&h->d_pt_A, cap))) return rc;
-  if ((rc = dev_alloc(&h->d_pt_lkl, cap))) return rc;
-  h->pt_cap = cap;
-  return NGHMM_OK;
+  if ((rc = h->d_pt_ind.reserve(cap)) || (rc = h->d_pt_F.reserve(cap)) || (rc = h->d_pt_A.reserve(cap))) return rc;
+  return h->d_pt_lkl.reserve(cap);
 }
 
 // the handle's own genotype likelihoods (log space), and those of its frequency-step site range
@@ -123,13 +112,13 @@ GlView own_gl(const nghmm_t* h) {
 
 int ensure_tmp(nghmm_t* h) {
   if (h->d_tmp) return NGHMM_OK;
-  return dev_alloc(&h->d_tmp, h->S * h->I * 2);
+  return h->d_tmp.alloc(h->S * h->I * 2);
 }
 
 int viterbi_scratch(nghmm_t* h, uint64_t* chunk, double** state) {
   int rc;
   const uint64_t room = viterbi_chunk_sites(h->S, h->I);
-  if (!h->d_vit && (rc = dev_alloc(&h->d_vit, (size_t)room * h->I * 4 + h->I * 2))) return rc;
+  if (!h->d_vit && (rc = h->d_vit.alloc((size_t)room * h->I * 4 + h->I * 2))) return rc;
   *chunk = viterbi_chunk_sites(h->S, h->I, h->fast.sw.viterbi_chunk);
   if (state) *state = h->d_vit + (size_t)*chunk * h->I * 4;
   return NGHMM_OK;
@@ -142,7 +131,7 @@ int ensure_marg(nghmm_t* h) {
   if (h->mode != NGHMM_MODE_FAST || h->marg_valid) return NGHMM_OK;
   int rc;
   if (!h->d_marg) {
-    if ((rc = dev_alloc(&h->d_marg, (size_t)h->I * h->S))) return rc;
+    if ((rc = h->d_marg.alloc((size_t)h->I * h->S))) return rc;
     HIP_TRY(hipMemsetAsync(h->d_marg, 0, (size_t)h->I * h->S * sizeof(double), h->stream));
   }
   if (!fast_post_to_site_major(h->fast, h->stream, h->d_marg)) return NGHMM_ERR_HIP;
@@ -269,28 +258,14 @@ int lane_setup(nghmm_t* h, int k, size_t n) {
   int rc;
   if (!L.ev0) {
     const unsigned evf = h->blocking_sync ? hipEventBlockingSync : hipEventDefault;
-    HIP_TRY(hipEventCreateWithFlags(&L.ev0, evf));
-    HIP_TRY(hipEventCreateWithFlags(&L.ev1, evf));
-    HIP_TRY(hipEventCreateWithFlags(&L.ev_done, evf | hipEventDisableTiming));
-    if ((rc = dev_alloc(&L.d_flags, (size_t)NFLAGS))) return rc;
-    HIP_TRY(hipHostMalloc((void**)&L.h_flags, NFLAGS * sizeof(int), hipHostMallocDefault));
+    if ((rc = L.ev0.create(evf)) || (rc = L.ev1.create(evf)) ||
+        (rc = L.ev_done.create(evf | hipEventDisableTiming)))
+      return rc;
+    if ((rc = L.d_flags.alloc(NFLAGS)) || (rc = L.h_flags.alloc(NFLAGS))) return rc;
   }
-  if (n > L.cap) {
-    if (L.d_lkl) (void)hipFree(L.d_lkl);
-    L.d_lkl = nullptr;
-    L.cap = 0;
-    const size_t cap = n + n / 4 + 1024;
-    if ((rc = dev_alloc(&L.d_lkl, cap))) return rc;
-    L.cap = cap;
-  }
-  if (n > L.h_cap) {
-    if (L.h_lkl) (void)hipHostFree(L.h_lkl);
-    L.h_lkl = nullptr;
-    L.h_cap = 0;
-    const size_t cap = n + n / 4 + 1024;
-    HIP_TRY(hipHostMalloc((void**)&L.h_lkl, cap * sizeof(double), hipHostMallocDefault));
-    L.h_cap = cap;
-  }
+  const size_t cap = n + n / 4 + 1024;
+  if (n > L.d_lkl.cap && (rc = L.d_lkl.reserve(cap))) return rc;
+  if (n > L.h_lkl.cap && (rc = L.h_lkl.reserve(cap))) return rc;
   return NGHMM_OK;
 }
 
@@ -379,7 +354,7 @@ static bool spans_on(const nghmm_t* h) { return h->mode != NGHMM_MODE_FAST || h-
 
 int bg_begin(nghmm_t* h) {
   int rc;
-  if (!h->d_flags_bg && (rc = dev_alloc(&h->d_flags_bg, (size_t)NFLAGS))) return rc;
+  if (!h->d_flags_bg && (rc = h->d_flags_bg.alloc(NFLAGS))) return rc;
   // (the last iteration's epilogue kernel has read the flags and cleared them again: no packet)
   if (!h->flags_bg_clear) HIP_TRY(hipMemsetAsync(h->d_flags_bg, 0, NFLAGS * sizeof(int), h->stream));
   h->flags_bg_clear = false;
@@ -399,9 +374,9 @@ int bg_open(nghmm_t* h, int slot, hipStream_t st) {
   if (h->bg_used == h->bg_spans.size()) {
     nghmm_handle::BgSpan sp;
     const unsigned evf = h->blocking_sync ? hipEventBlockingSync : hipEventDefault;
-    HIP_TRY(hipEventCreateWithFlags(&sp.ev0, evf));
-    HIP_TRY(hipEventCreateWithFlags(&sp.ev1, evf));
-    h->bg_spans.push_back(sp);
+    int rc;
+    if ((rc = sp.ev0.create(evf)) || (rc = sp.ev1.create(evf))) return rc;
+    h->bg_spans.push_back(std::move(sp));
   }
   h->bg_spans[h->bg_used].slot = slot;
   HIP_TRY(hipEventRecord(h->bg_spans[h->bg_used].ev0, st));
@@ -445,6 +420,40 @@ int ensure_emissions(nghmm_t* h) {
 }
 
 }  // namespace capi
+
+// Drains the handle's streams and releases the fast-mode state; the members then release
+// themselves, buffers before events and streams (capi_internal.hpp).
+nghmm_handle::~nghmm_handle() {
+  (void)hipSetDevice(device);
+  for (hipStream_t s : {stream.p, aux_stream.p, g_xstream.p})
+    if (s) (void)hipStreamSynchronize(s);
+  fast_destroy(fast);
+}
+
+// What every handle owns, a replica too (h->I, S, mode, blocking_sync are set): its stream and
+// timing events, the error flags, the parameters and their host copies, and in exact mode the
+// emissions, the forward variable and the posteriors (zero before the first E-step).
+static int alloc_own_state(nghmm_t* h) {
+  int rc;
+  if ((rc = h->stream.create())) return rc;
+  const unsigned evf = h->blocking_sync ? hipEventBlockingSync : hipEventDefault;
+  if ((rc = h->ev0.create(evf)) || (rc = h->ev1.create(evf))) return rc;
+  if (h->blocking_sync && (rc = h->ev_sync.create(evf | hipEventDisableTiming))) return rc;
+  const size_t cells = (size_t)h->I * h->S;
+  if ((rc = h->d_flags.alloc(NFLAGS)) || (rc = h->d_freq.alloc(h->S)) || (rc = h->d_indF.alloc(h->I)) ||
+      (rc = h->d_alpha.alloc(h->I)) || (rc = h->d_ind_lkl.alloc(h->I)))
+    return rc;
+  if (h->mode == NGHMM_MODE_EXACT) {
+    if ((rc = h->d_eprob.alloc(cells * 2)) || (rc = h->d_fw.alloc((cells + h->I) * 2)) ||
+        (rc = h->d_marg.alloc(cells)))
+      return rc;
+    HIP_TRY(hipMemset(h->d_marg, 0, cells * sizeof(double)));
+  }
+  HIP_TRY(hipMemset(h->d_freq, 0, h->S * sizeof(double)));
+  h->h_indF.assign(h->I, 0.0);
+  h->h_alpha.assign(h->I, 0.0);
+  return NGHMM_OK;
+}
 
 
 extern "C" {
@@ -502,14 +511,12 @@ int nghmm_create(nghmm_t** out, uint64_t n_ind, uint64_t n_sites, int device, in
   int rc = NGHMM_OK;
   do {
     if (hipSetDevice(device) != hipSuccess) { rc = NGHMM_ERR_HIP; break; }
-    if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) { rc = NGHMM_ERR_HIP; break; }
-    if (hipEventCreate(&h->ev0) != hipSuccess || hipEventCreate(&h->ev1) != hipSuccess) { rc = NGHMM_ERR_HIP; break; }
+    if ((rc = alloc_own_state(h))) break;
     const size_t cells = (size_t)n_ind * n_sites;
     if (packed) {
-      if ((rc = dev_alloc(&h->d_codes, cells / 16 + 2))) break;
-      if ((rc = dev_alloc(&h->d_cls_log, (size_t)12))) break;
-      if ((rc = dev_alloc(&h->d_uniform, (size_t)1))) break;
-      if ((rc = dev_alloc(&h->d_flags, (size_t)NFLAGS))) break;
+      if ((rc = h->d_codes.alloc(cells / 16 + 2))) break;
+      if ((rc = h->d_cls_log.alloc(12))) break;
+      if ((rc = h->d_uniform.alloc(1))) break;
       // the prepared likelihoods of the four classes: what the reference's reader and its two
       // normalisations make of a called genotype 0 / 1 / 2 and of a missing one
       // (shared/read_data.cpp:21,88-98; ngsF-HMM.cpp:117); row 3 is replaced by the value the
@@ -523,34 +530,19 @@ int nghmm_create(nghmm_t** out, uint64_t n_ind, uint64_t n_sites, int device, in
                          h->stream) != hipSuccess ||
           sync_stream(h) != hipSuccess) { rc = NGHMM_ERR_HIP; break; }
     } else {
-      if ((rc = dev_alloc(&h->d_gl, cells * 3))) break;
-      if ((rc = dev_alloc(&h->d_flags, (size_t)NFLAGS))) break;
+      if ((rc = h->d_gl.alloc(cells * 3))) break;
     }
-    if ((rc = dev_alloc(&h->d_pos, n_sites))) break;
-    if ((rc = dev_alloc(&h->d_freq, n_sites))) break;
-    if ((rc = dev_alloc(&h->d_indF, n_ind))) break;
-    if ((rc = dev_alloc(&h->d_alpha, n_ind))) break;
-    if ((rc = dev_alloc(&h->d_ind_lkl, n_ind))) break;
-    if (mode == NGHMM_MODE_EXACT) {
-      if ((rc = dev_alloc(&h->d_eprob, cells * 2))) break;
-      if ((rc = dev_alloc(&h->d_fw, (cells + n_ind) * 2))) break;
-      if ((rc = dev_alloc(&h->d_marg, cells))) break;
-      if (hipMemset(h->d_marg, 0, cells * sizeof(double)) != hipSuccess) { rc = NGHMM_ERR_HIP; break; }
-    }
-    if (hipMemset(h->d_freq, 0, n_sites * sizeof(double)) != hipSuccess) { rc = NGHMM_ERR_HIP; break; }
-    h->h_indF.assign(n_ind, 0.0);
-    h->h_alpha.assign(n_ind, 0.0);
+    if ((rc = h->d_pos.alloc(n_sites))) break;
     if (mode == NGHMM_MODE_FAST && !fast_create(h->fast, n_ind, n_sites, packed)) { rc = NGHMM_ERR_NOMEM; break; }
   } while (0);
   if (rc != NGHMM_OK) {
     if (g_last_error.empty()) set_error("nghmm_create failed (%d)", rc);
-    nghmm_destroy(h);
+    delete h;
     return rc;
   }
   *out = h;
   return NGHMM_OK;
 }
-
 
 int nghmm_destroy(nghmm_t* h) {
   if (!h) return NGHMM_OK;
@@ -561,49 +553,7 @@ int nghmm_destroy(nghmm_t* h) {
   (void)hipSetDevice(h->device);
   if (h->stream) (void)hipStreamSynchronize(h->stream);
   chain_release(h);
-  void* own[] = {h->d_freq, h->d_eprob, h->d_fw, h->d_marg, h->d_indF,
-                 h->d_alpha, h->d_ind_lkl, h->d_flags, h->d_pt_ind, h->d_pt_F, h->d_pt_A,
-                 h->d_pt_lkl, h->d_bp, h->d_path_sites, h->d_path, h->d_tmp, h->d_passes, h->d_vit,
-                 h->d_gl_shard, h->d_geno, h->d_text, h->d_codes_shard, h->d_uniform, h->d_stage,
-                 h->d_freq_new, h->d_hap, h->d_tseg, h->d_trec, h->d_samp, h->d_info,
-                 h->d_stage8, h->g_send, h->g_recv, h->g_freq_own, h->g_freq_all};
-  if (h->g_xstream) (void)hipStreamDestroy(h->g_xstream);
-  if (h->d_flags_bg) (void)hipFree(h->d_flags_bg);
-  for (auto& sp : h->bg_spans)
-    for (hipEvent_t e : {sp.ev0, sp.ev1})
-      if (e) (void)hipEventDestroy(e);
-  for (auto& L : h->lane) {
-    if (L.d_lkl) (void)hipFree(L.d_lkl);
-    if (L.d_flags) (void)hipFree(L.d_flags);
-    if (L.h_lkl) (void)hipHostFree(L.h_lkl);
-    if (L.h_flags) (void)hipHostFree(L.h_flags);
-    for (hipEvent_t e : {L.ev0, L.ev1, L.ev_done})
-      if (e) (void)hipEventDestroy(e);
-  }
-  for (void* p : own)
-    if (p) (void)hipFree(p);
-  if (!h->parent) {
-    void* data[] = {h->d_gl, h->d_pos, h->d_codes, h->d_cls_log};
-    for (void* p : data)
-      if (p) (void)hipFree(p);
-  } else {
-    h->parent->n_replicas.fetch_sub(1);
-  }
-  fast_destroy(h->fast);
-  for (hipEvent_t e : {h->aux_ev0, h->aux_ev1, h->aux_go, h->aux_done})
-    if (e) (void)hipEventDestroy(e);
-  for (hipEvent_t e : h->aux_piece_ev)
-    if (e) (void)hipEventDestroy(e);
-  for (hipEvent_t e : h->aux_estep_ev)
-    if (e) (void)hipEventDestroy(e);
-  if (h->d_aux_params) (void)hipFree(h->d_aux_params);
-  if (h->h_flags_pin) (void)hipHostFree(h->h_flags_pin);
-  if (h->h_lkl_pin) (void)hipHostFree(h->h_lkl_pin);
-  if (h->aux_stream) (void)hipStreamDestroy(h->aux_stream);
-  if (h->ev0) (void)hipEventDestroy(h->ev0);
-  if (h->ev1) (void)hipEventDestroy(h->ev1);
-  if (h->ev_sync) (void)hipEventDestroy(h->ev_sync);
-  if (h->stream) (void)hipStreamDestroy(h->stream);
+  if (h->parent) h->parent->n_replicas.fetch_sub(1);
   delete h;
   return NGHMM_OK;
 }
@@ -631,47 +581,25 @@ int nghmm_create_replica(nghmm_t** out, nghmm_t* parent) {
   h->I_tot = h->I;
   h->S_own = h->S;
   h->parent = parent;
-  parent->n_replicas.fetch_add(1);
   // replicas run their EM iterations side by side from host threads of their own: each M-step
   // keeps to its thread (R pools of OpenMP workers would fight over the cores)
   parent->batch.set_max_threads(1);
   h->batch.set_max_threads(1);
-  h->d_gl = parent->d_gl;
-  h->d_pos = parent->d_pos;
-  h->d_codes = parent->d_codes;
-  h->d_cls_log = parent->d_cls_log;
-  const uint64_t n_ind = h->I, n_sites = h->S;
-  do {
-    if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) { rc = NGHMM_ERR_HIP; break; }
-    // replicas are driven from one host thread each: wait without spinning
-    h->blocking_sync = true;
-    const unsigned evf = h->blocking_sync ? hipEventBlockingSync : hipEventDefault;
-    if (hipEventCreateWithFlags(&h->ev0, evf) != hipSuccess ||
-        hipEventCreateWithFlags(&h->ev1, evf) != hipSuccess ||
-        hipEventCreateWithFlags(&h->ev_sync, evf | hipEventDisableTiming) != hipSuccess) { rc = NGHMM_ERR_HIP; break; }
-    const size_t cells = (size_t)n_ind * n_sites;
-    if ((rc = dev_alloc(&h->d_flags, (size_t)NFLAGS))) break;
-    if ((rc = dev_alloc(&h->d_freq, n_sites))) break;
-    if ((rc = dev_alloc(&h->d_indF, n_ind))) break;
-    if ((rc = dev_alloc(&h->d_alpha, n_ind))) break;
-    if ((rc = dev_alloc(&h->d_ind_lkl, n_ind))) break;
-    if (h->mode == NGHMM_MODE_EXACT) {
-      if ((rc = dev_alloc(&h->d_eprob, cells * 2))) break;
-      if ((rc = dev_alloc(&h->d_fw, (cells + n_ind) * 2))) break;
-      if ((rc = dev_alloc(&h->d_marg, cells))) break;
-      if (hipMemset(h->d_marg, 0, cells * sizeof(double)) != hipSuccess) { rc = NGHMM_ERR_HIP; break; }
-    }
-    if (hipMemset(h->d_freq, 0, n_sites * sizeof(double)) != hipSuccess) { rc = NGHMM_ERR_HIP; break; }
-    h->h_indF.assign(n_ind, 0.0);
-    h->h_alpha.assign(n_ind, 0.0);
-    if (h->mode == NGHMM_MODE_FAST && !fast_create_replica(h->fast, parent->fast)) { rc = NGHMM_ERR_NOMEM; break; }
-    h->loaded = true;
-  } while (0);
+  h->d_gl.borrow(parent->d_gl);
+  h->d_pos.borrow(parent->d_pos);
+  h->d_codes.borrow(parent->d_codes);
+  h->d_cls_log.borrow(parent->d_cls_log);
+  h->blocking_sync = true;   // ... and wait for their streams without spinning
+  if ((rc = alloc_own_state(h)) == NGHMM_OK && h->mode == NGHMM_MODE_FAST &&
+      !fast_create_replica(h->fast, parent->fast))
+    rc = NGHMM_ERR_NOMEM;
   if (rc != NGHMM_OK) {
     if (g_last_error.empty()) set_error("nghmm_create_replica failed (%d)", rc);
-    nghmm_destroy(h);
+    delete h;
     return rc;
   }
+  h->loaded = true;
+  parent->n_replicas.fetch_add(1);   // (nghmm_destroy of the replica takes it back)
   *out = h;
   return NGHMM_OK;
 }
@@ -1024,10 +952,10 @@ struct MstepRun {
       ~AuxDrain() { if (s) (void)hipStreamSynchronize(s); }
     } drain;
     if (overlap) {
-      if (!h->aux_stream) HIP_TRY(hipStreamCreateWithFlags(&h->aux_stream, hipStreamNonBlocking));
-      if (!h->aux_go) HIP_TRY(hipEventCreateWithFlags(&h->aux_go, hipEventDisableTiming));
-      if (!h->aux_done) HIP_TRY(hipEventCreateWithFlags(&h->aux_done, hipEventDisableTiming));
-      if (!h->d_flags_bg && (rc = dev_alloc(&h->d_flags_bg, (size_t)NFLAGS))) return rc;
+      if (!h->aux_stream && (rc = h->aux_stream.create())) return rc;
+      if (!h->aux_go && (rc = h->aux_go.create(hipEventDisableTiming))) return rc;
+      if (!h->aux_done && (rc = h->aux_done.create(hipEventDisableTiming))) return rc;
+      if (!h->d_flags_bg && (rc = h->d_flags_bg.alloc(NFLAGS))) return rc;
       bg_stream = drain.s = h->aux_stream;
     }
     h->ms[SLOT_BFGS] = 0;
@@ -1180,8 +1108,7 @@ struct MstepRun {
       rc = map_flags(f);
     } else {
       if (lkl_out) {  // (through pinned memory: the copy waits for nothing, bg_finish waits once for everything)
-        if (!h->h_lkl_pin)
-          HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&h->h_lkl_pin), h->I * sizeof(double), hipHostMallocDefault));
+        if (!h->h_lkl_pin && (rc = h->h_lkl_pin.alloc(h->I))) return rc;
         HIP_TRY(hipMemcpyAsync(h->h_lkl_pin, h->d_ind_lkl, h->I * sizeof(double), hipMemcpyDeviceToHost,
                                h->stream));
       }
@@ -1462,8 +1389,8 @@ static int mstep_freq_ld_impl(nghmm_t* h, int freq_est, int e_prob) {
     return NGHMM_ERR_ARG;
   }
   int rc;
-  if (!h->d_freq_new && (rc = dev_alloc(&h->d_freq_new, (size_t)h->S))) return rc;
-  if (!h->d_hap && (rc = dev_alloc(&h->d_hap, (size_t)h->S * 4))) return rc;
+  if (!h->d_freq_new && (rc = h->d_freq_new.alloc(h->S))) return rc;
+  if (!h->d_hap && (rc = h->d_hap.alloc((size_t)h->S * 4))) return rc;
   if ((rc = clear_flags(h))) return rc;
   if (!exact && (rc = ensure_marg(h))) return rc;  // site-major posteriors
   // the first site, or (freq_est 1) every site, by est_maf (EM.cpp:242-244)
@@ -1583,14 +1510,15 @@ int nghmm_iter_em(nghmm_t* h, int freq_est, int indF_fixed, int alpha_fixed, dou
     // reference's E-step comes before its M-step (EM.cpp:147-201).
     constexpr bool overlap_estep = true;
     if (!h->aux_stream) {
-      HIP_TRY(hipStreamCreateWithFlags(&h->aux_stream, hipStreamNonBlocking));
-      HIP_TRY(hipEventCreate(&h->aux_ev0));
-      HIP_TRY(hipEventCreate(&h->aux_ev1));
-      HIP_TRY(hipEventCreateWithFlags(&h->aux_go, hipEventDisableTiming));
-      for (auto& e : h->aux_piece_ev) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-      for (auto& e : h->aux_estep_ev) HIP_TRY(hipEventCreate(&e));
-      if ((rc = dev_alloc(&h->d_aux_params, (size_t)h->I * 2))) return rc;
-      if (!h->d_flags_bg && (rc = dev_alloc(&h->d_flags_bg, (size_t)NFLAGS))) return rc;
+      if ((rc = h->aux_stream.create()) || (rc = h->aux_ev0.create()) || (rc = h->aux_ev1.create()) ||
+          (rc = h->aux_go.create(hipEventDisableTiming)))
+        return rc;
+      for (auto& e : h->aux_piece_ev)
+        if ((rc = e.create(hipEventDisableTiming))) return rc;
+      for (auto& e : h->aux_estep_ev)
+        if ((rc = e.create())) return rc;
+      if ((rc = h->d_aux_params.alloc((size_t)h->I * 2))) return rc;
+      if (!h->d_flags_bg && (rc = h->d_flags_bg.alloc(NFLAGS))) return rc;
     }
     // whatever happens from here on, nothing may be left running on the second stream when
     // this call returns (the caller may destroy the handle or load other data next)
@@ -1678,9 +1606,9 @@ int nghmm_viterbi(nghmm_t* h, uint8_t* path) {
   if ((rc = use_device(h))) return rc;
   const size_t cells = (size_t)h->I * h->S;
   const size_t blocked = viterbi_blocked_bytes(h->S, h->I);
-  if (!h->d_bp && (rc = dev_alloc(&h->d_bp, blocked + h->I))) return rc;
-  if (!h->d_path_sites && (rc = dev_alloc(&h->d_path_sites, blocked))) return rc;
-  if (!h->d_path && (rc = dev_alloc(&h->d_path, cells))) return rc;
+  if (!h->d_bp && (rc = h->d_bp.alloc(blocked + h->I))) return rc;
+  if (!h->d_path_sites && (rc = h->d_path_sites.alloc(blocked))) return rc;
+  if (!h->d_path && (rc = h->d_path.alloc(cells))) return rc;
   uint64_t chunk;
   if ((rc = viterbi_scratch(h, &chunk))) return rc;
   tic(h);
@@ -1705,16 +1633,17 @@ int nghmm_viterbi(nghmm_t* h, uint8_t* path) {
 }
 
 void* nghmm_alloc_host(uint64_t bytes) {
-  void* p = nullptr;
-  if (bytes == 0 || hipHostMalloc(&p, bytes, hipHostMallocDefault) != hipSuccess) {
+  PinBuf<uint8_t> b;   // (the caller holds the raw pointer from here to nghmm_free_host)
+  if (bytes == 0 || b.alloc(bytes) != NGHMM_OK) {
     (void)hipGetLastError();
     return nullptr;
   }
-  return p;
+  return b.release();
 }
 
 void nghmm_free_host(void* p) {
-  if (p) (void)hipHostFree(p);
+  PinBuf<uint8_t> b;
+  b.adopt(static_cast<uint8_t*>(p));
 }
 
 int nghmm_set_switch(nghmm_t* h, const char* name, long value) {
