@@ -385,6 +385,81 @@ int nghmm_obs_info(nghmm_t* h, const double* F, const double* alpha, nghmm_info*
  * only.) */
 int nghmm_chain_obs_info(nghmm_t** hs, int n, const double* F, const double* alpha, nghmm_info* out);
 
+/* ---- IBD per region and per site ----
+ * The two reductions of the decoded path [I][S] and the posteriors [I][S] that an .ibd file is
+ * most often read back for, made on the device where the run left both arrays, in one pass over
+ * them: along the sites, per individual and REGION -- the share of a chromosome or of a window
+ * that is IBD (F_ROH per chromosome, a genome scan) and its IBD length in Mb --, and along the
+ * individuals, per SITE -- how many individuals are IBD there (ROH islands).  (The reference has
+ * no such function.)
+ *
+ * Regions are half-open ranges of sites [region_begin[r], region_end[r]) with begin < end <= S,
+ * sorted, not overlapping; gaps are allowed, and a site in no region counts for no region.  Site
+ * indices are handle-local for one handle and global for a chain.  A region may span chromosome
+ * starts: the vit_mb rule skips the infinite distance there.  The site before a region's first
+ * site never contributes to vit_mb.
+ *
+ * `what` is a bit mask of the sources:
+ *   NGHMM_SUMMARY_VITERBI    path[i][s] of the last nghmm_viterbi / nghmm_chain_viterbi decode of
+ *                            the loaded data (NGHMM_ERR_ARG if there was none since the load)
+ *   NGHMM_SUMMARY_POSTERIOR  marg_prob[i][s][1], the values nghmm_get_posteriors returns (zeros
+ *                            before the first E-step); threshold in (0, 1], else -- NaN included --
+ *                            NGHMM_ERR_ARG (the threshold is not looked at without this source)
+ * The fields of a source that was not asked for are 0.  what == 0 or an unknown bit:
+ * NGHMM_ERR_ARG.
+ *
+ * regions [I][n_regions] (host) is NULL iff n_regions == 0 (then region_begin and region_end are
+ * not read); sites [S] (host) may be NULL; at least one of the two is not.  NGHMM_ERR_ARG also for
+ * a handle without data, for unsorted, overlapping or empty regions, for end > S, and for a NULL
+ * mismatch.
+ *
+ * No float atomics; every double is added in one fixed order that does not depend on the call:
+ * the same bits on every call.  post_sum and vit_mb of a region: the region is cut at the
+ * multiples of 2048 sites (of the handle's own sites); within a piece the terms are added to 0 in
+ * site order; the pieces are added in site order, the first one's value first.  post_sum of a
+ * site: the individuals in blocks of 64; within a block (filled up with zeros) the 64 values are
+ * added as a butterfly -- x_i += x_{i ^ 32}, then ^ 16, 8, 4, 2, 1 --; the blocks are added in
+ * order, the first one's value first.  
+ *
+ * Read-only: parameters, posteriors, the Viterbi path, checkpoints and an M-step planned in
+ * advance stay as they are; an EM iteration after the call gives the bits it would have given
+ * without it.  Device scratch grows with I x (n_regions + S / 2048) and with S
+ * (NGHMM_ERR_NOMEM when it cannot be had) and is kept by the handle.
+ *
+ * Groups of individual shards (nghmm_group_*) are out of scope: every member summarises its own
+ * individuals, and a site's records of the members are the caller's to add. */
+enum { NGHMM_SUMMARY_VITERBI = 1, NGHMM_SUMMARY_POSTERIOR = 2 };
+typedef struct nghmm_region_stat {  /* 32 bytes; one per (individual, region) */
+  uint64_t vit_sites;   /* sites of the region with path[i][s] == 1 */
+  uint64_t post_sites;  /* sites of the region with marg_prob[i][s][1] >= threshold */
+  double post_sum;      /* sum of marg_prob[i][s][1] over the region's sites */
+  double vit_mb;        /* sum of d_s over the region's sites s > region begin with
+                           path[i][s-1] == path[i][s] == 1 and d_s finite: IBD length in Mb,
+                           the per-region counterpart of nghmm_path_stats.ibd_mb */
+} nghmm_region_stat;
+typedef struct nghmm_site_stat {    /* 16 bytes; one per site */
+  uint32_t vit_count;   /* individuals with path[i][s] == 1 */
+  uint32_t post_count;  /* individuals with marg_prob[i][s][1] >= threshold */
+  double post_sum;      /* sum over individuals of marg_prob[i][s][1] */
+} nghmm_site_stat;
+#ifdef __cplusplus
+static_assert(sizeof(nghmm_region_stat) == 32 && sizeof(nghmm_site_stat) == 16, "record sizes");
+#endif
+int nghmm_ibd_summary(nghmm_t* h, int what, double threshold, uint64_t n_regions,
+                      const uint64_t* region_begin, const uint64_t* region_end,
+                      nghmm_region_stat* regions, nghmm_site_stat* sites);
+/* The same over a chain of site shards (nghmm_chain_setup, else NGHMM_ERR_ARG): global site
+ * indices; sites [all sites] is the concatenation of the shards' records (each computed on its
+ * own device exactly as for one handle: the same bytes); a region that crosses a shard boundary
+ * is one region -- every shard reduces its part of it, the parts are added on the host in rank
+ * order --, and vit_mb at a shard's first site looks at the last decoded state of the shard
+ * before: one byte per individual, moved through the host the way nghmm_viterbi_shard_back moves
+ * state_before.  (Chains of more than one handle are fast mode only, as nghmm_chain_setup
+ * requires.) */
+int nghmm_chain_ibd_summary(nghmm_t** hs, int n, int what, double threshold, uint64_t n_regions,
+                            const uint64_t* region_begin, const uint64_t* region_end,
+                            nghmm_region_stat* regions, nghmm_site_stat* sites);
+
 /* ---- multi-GPU (individuals sharded over ranks) ----
  * The allele-frequency step needs every individual of a site.  A rank owns the
  * individuals [ind_begin, ind_begin + n_ind) of n_ind_total for all sites, and

@@ -17,9 +17,13 @@ an :class:`NgsFHMM` raises.
 from .hmm import (NgsFHMM, NgsFHMMError, Group, Chain, MODE_EXACT, MODE_FAST, GENO_PACKED, LD_INTENDED, EPROB_LD, library_path,
                   load_library,
                   build_library, bed_lines, TRACTS_VITERBI, TRACTS_POSTERIOR, PATH_STATS_DTYPE,
-                  path_stats_summary, INFO_DTYPE, std_errors)
+                  path_stats_summary, INFO_DTYPE, std_errors, SUMMARY_VITERBI, SUMMARY_POSTERIOR,
+                  SUMMARY_SEGMENT_SITES, REGION_STAT_DTYPE, SITE_STAT_DTYPE, chromosome_regions,
+                  window_regions)
 from . import simulate
 
 __all__ = ["NgsFHMM", "NgsFHMMError", "Group", "Chain", "MODE_EXACT", "MODE_FAST", "GENO_PACKED", "LD_INTENDED", "EPROB_LD", "library_path",
            "load_library", "build_library", "simulate", "bed_lines", "TRACTS_VITERBI", "TRACTS_POSTERIOR",
-           "PATH_STATS_DTYPE", "path_stats_summary", "INFO_DTYPE", "std_errors"]
+           "PATH_STATS_DTYPE", "path_stats_summary", "INFO_DTYPE", "std_errors", "SUMMARY_VITERBI",
+           "SUMMARY_POSTERIOR", "SUMMARY_SEGMENT_SITES", "REGION_STAT_DTYPE", "SITE_STAT_DTYPE",
+           "chromosome_regions", "window_regions"]

@@ -1,6 +1,6 @@
 // capi_internal.hpp -- what the translation units of the C ABI share: the handle, error plumbing,
 // and the helpers every entry point uses.  nghmm_capi.hip (handle life cycle, single-handle EM),
-// capi_load.hip (loaders), capi_output.hip (read-back and output formatting), capi_tracts.hip, capi_sample.hip, capi_info.hip and
+// capi_load.hip (loaders), capi_output.hip (read-back and output formatting), capi_tracts.hip, capi_sample.hip, capi_info.hip, capi_summary.hip and
 // capi_multi.hip (individual shards, site shards, groups and chains of handles) implement include/nghmm.h.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -27,6 +27,7 @@
 #include "capi_owners.hpp"
 #include "kernels.hpp"
 #include "kernels_fast.hpp"
+#include "kernels_summary.hpp"
 
 using namespace nghmm;
 
@@ -104,6 +105,8 @@ struct nghmm_handle {
   DevScratch<uint8_t> d_samp;
   // observed information (capi_info.hip): the points, the waves' jets, the records
   DevScratch<uint8_t> d_info;
+  // region and site summaries (capi_summary.hip): piece, region and site records, the pieces
+  DevScratch<uint8_t> d_summ;
   DevBuf<double> d_freq_new, d_hap;  // --freq_est 2 as intended: [S], [S][4]
 
   // multi-GPU shard
@@ -220,5 +223,22 @@ int tracts_to_host(nghmm_t* h, int source, double threshold, uint64_t min_sites,
                    std::vector<nghmm_tract>& out);
 // source / threshold of nghmm_ibd_tracts; sets the error message
 int tracts_check_args(nghmm_t* h, int source, double threshold, const char* who);
+// nghmm_ibd_summary's argument checks (capi_summary.hip); they set the error message
+int summary_check_source(nghmm_t* h, int what, double threshold, const char* who);
+int summary_check_regions(uint64_t S, uint64_t I, uint64_t n_regions, const uint64_t* begin,
+                          const uint64_t* end, const void* regions, const void* sites,
+                          const char* who);
+// a region in handle-local sites; first: begin is the region's own first site (false: the region
+// goes on from the site shard before, whose last decoded state is summary_to_host's prev_state)
+struct SummaryRegion {
+  uint64_t begin, end;
+  bool first;
+};
+// the summary of one handle to the host: regions [I][regs.size()] (NULL iff there are none),
+// sites [S] (may be NULL); prev_state [I] (host, may be NULL = all 0)
+int summary_to_host(nghmm_t* h, int what, double thr, const std::vector<SummaryRegion>& regs,
+                    const uint8_t* prev_state, nghmm_region_stat* regions, nghmm_site_stat* sites);
+// out[I] (host) = the decoded state at the handle's last site
+int summary_last_state(nghmm_t* h, uint8_t* out);
 
 }  // namespace capi

@@ -764,3 +764,66 @@ int nghmm_chain_ibd_tracts(nghmm_t** hs, int n, int source, double threshold, ui
   return NGHMM_OK;
 }
 
+// Region and site summaries over a chain: every handle summarises its own sites -- the site
+// records as they are, one after the other; of every region the part inside its range, with the
+// last decoded state of the handle before in front of its first site -- and the host adds a
+// region's parts in rank order.
+int nghmm_chain_ibd_summary(nghmm_t** hs, int n, int what, double threshold, uint64_t n_regions,
+                            const uint64_t* region_begin, const uint64_t* region_end,
+                            nghmm_region_stat* regions, nghmm_site_stat* sites) {
+  g_last_error.clear();
+  if (!is_chain(hs, n)) {
+    set_error("nghmm_chain_ibd_summary: call nghmm_chain_setup on these handles first");
+    return NGHMM_ERR_ARG;
+  }
+  if (n == 1)
+    return nghmm_ibd_summary(hs[0], what, threshold, n_regions, region_begin, region_end, regions, sites);
+  int rc;
+  uint64_t S_tot = 0;
+  for (int r = 0; r < n; ++r) {
+    if ((rc = summary_check_source(hs[r], what, threshold, "nghmm_chain_ibd_summary"))) return rc;
+    S_tot += hs[r]->S;
+  }
+  const uint64_t I = hs[0]->I, R = n_regions;
+  if ((rc = summary_check_regions(S_tot, I, R, region_begin, region_end, regions, sites,
+                                  "nghmm_chain_ibd_summary")))
+    return rc;
+  if (R) std::memset(regions, 0, (size_t)I * R * sizeof(nghmm_region_stat));
+  std::vector<uint8_t> state(I);
+  std::vector<SummaryRegion> regs;
+  std::vector<nghmm_region_stat> part;
+  uint64_t base = 0, r0 = 0;   // r0: the first region that does not end before this handle's sites
+  for (int q = 0; q < n; ++q) {
+    nghmm_t* h = hs[q];
+    const uint64_t lo = base, hi = base + h->S;
+    while (r0 < R && region_end[r0] <= lo) ++r0;
+    regs.clear();
+    for (uint64_t r = r0; r < R && region_begin[r] < hi; ++r) {
+      const uint64_t a = region_begin[r] > lo ? region_begin[r] : lo, b = region_end[r] < hi ? region_end[r] : hi;
+      regs.push_back({a - lo, b - lo, region_begin[r] >= lo});
+    }
+    const bool need_state = q > 0 && (what & NGHMM_SUMMARY_VITERBI) && !regs.empty() && !regs[0].first;
+    if (need_state && (rc = summary_last_state(hs[q - 1], state.data()))) return rc;
+    part.resize((size_t)I * regs.size());
+    if (!regs.empty() || sites) {
+      if ((rc = summary_to_host(h, what, threshold, regs, need_state ? state.data() : nullptr,
+                                regs.empty() ? nullptr : part.data(), sites ? sites + lo : nullptr)))
+        return rc;
+    }
+    for (uint64_t i = 0; i < I; ++i)
+      for (uint64_t k = 0; k < regs.size(); ++k) {
+        nghmm_region_stat& t = regions[i * R + r0 + k];
+        const nghmm_region_stat& a = part[i * regs.size() + k];
+        if (regs[k].first) {   // the region's first part: its value, not 0 + its value
+          t = a;
+        } else {
+          t.vit_sites += a.vit_sites;
+          t.post_sites += a.post_sites;
+          t.post_sum += a.post_sum;
+          t.vit_mb += a.vit_mb;
+        }
+      }
+    base = hi;
+  }
+  return NGHMM_OK;
+}

@@ -13,7 +13,10 @@
 // (PREFIX.ibd.samples: the statistics of R IBD paths per individual drawn from the joint posterior
 // after the final decode; PREFIX.sample_kk.ibd: the first K of them), --indF_se (PREFIX.indF.se:
 // standard errors of indF and alpha from the observed information at the final parameters,
-// conditional on the allele frequencies).  --n_threads (the
+// conditional on the allele frequencies), --ibd_summary [--summary_window N] [--summary_thresh P]
+// (PREFIX.ibd.regions: per individual and chromosome -- or window of N sites -- the share of sites
+// that are IBD and the IBD length; PREFIX.ibd.sites: per site the number of individuals that are
+// IBD; both reduced on the device after the final decode).  --n_threads (the
 // reference's pool size) sets the host threads used for input normalisation and output
 // formatting; results do not depend on it.
 #include <fcntl.h>
@@ -49,6 +52,8 @@
 #pragma weak nghmm_chain_sample_paths
 // ... and without the observed-information entry: --indF_se then stops with a message
 #pragma weak nghmm_chain_obs_info
+// ... and without the summary entry: --ibd_summary then stops with a message
+#pragma weak nghmm_chain_ibd_summary
 
 namespace {
 
@@ -99,6 +104,12 @@ struct Params {  // ngsF-HMM.hpp:13-52
   // their correlation from the observed information at the final parameters and frequencies
   // (nghmm_chain_obs_info), the log-likelihood and its gradient there
   bool indF_se = false;
+  // --ibd_summary: PREFIX.ibd.regions and PREFIX.ibd.sites after the final decode
+  // (nghmm_chain_ibd_summary); regions are the chromosomes, or with --summary_window N windows of
+  // N sites that restart at every chromosome start; --summary_thresh P: the posterior threshold
+  bool ibd_summary = false;
+  uint64_t summary_window = 0;
+  double summary_thresh = 0.5;
   std::vector<uint64_t> site_pos;           // [S] the .pos file's integer positions
   std::vector<uint64_t> chrom_first;        // first site of every run of one chromosome name
   std::vector<std::string> chrom_name;      // ... and that name
@@ -1396,6 +1407,70 @@ void write_indF_se(const Params& P, Cohort& C) {
   if (fclose(fh) != 0) fatal(__FUNCTION__, "cannot write the standard-error output file!");
 }
 
+// PREFIX.ibd.regions: a header line, then per individual and region "IND_ID chr first_pos last_pos
+// n_sites vit_sites vit_share post_sites post_mean vit_mb" (tab-separated, ordered by individual,
+// then region; IDs as --ibd_bed names them; chromosome names and positions from the --pos file):
+// the sites of the region that are IBD in the decoded path, their share, the sites whose posterior
+// reaches --summary_thresh, the mean posterior, the IBD length in Mb.  Regions are the chromosomes,
+// or windows of --summary_window sites that restart at every chromosome start.
+// PREFIX.ibd.sites: a header line, then per site "chr pos vit_count post_count post_mean": the
+// individuals that are IBD there, by the path and by the threshold, and the mean posterior.
+void write_ibd_summary(const Params& P, Cohort& C) {
+  if (!nghmm_chain_ibd_summary)
+    fatal(__FUNCTION__, "--ibd_summary: the library has no nghmm_chain_ibd_summary!");
+  const uint64_t I = P.n_ind, S = P.n_sites;
+  std::vector<uint64_t> begin, end;
+  std::vector<size_t> chrom;   // the chromosome run of every region
+  for (size_t c = 0; c < P.chrom_first.size(); c++) {
+    const uint64_t a = P.chrom_first[c], b = c + 1 < P.chrom_first.size() ? P.chrom_first[c + 1] : S;
+    const uint64_t w = P.summary_window ? P.summary_window : b - a;
+    for (uint64_t lo = a; lo < b; lo += w) {
+      begin.push_back(lo);
+      end.push_back(b - lo < w ? b : lo + w);
+      chrom.push_back(c);
+    }
+  }
+  const uint64_t R = begin.size();
+  std::vector<nghmm_region_stat> reg((size_t)I * R);
+  std::vector<nghmm_site_stat> sites(S);
+  check(nghmm_chain_ibd_summary(C.hs.data(), C.n(), NGHMM_SUMMARY_VITERBI | NGHMM_SUMMARY_POSTERIOR,
+                                P.summary_thresh, R, begin.data(), end.data(), reg.data(), sites.data()),
+        "ibd_summary");
+  std::string name = P.prefix + ".ibd.regions";
+  FILE* fh = fopen(name.c_str(), "w");
+  if (!fh) fatal(__FUNCTION__, "cannot open region summary output file!");
+  setvbuf(fh, nullptr, _IOFBF, 1 << 22);
+  fputs("ind\tchr\tfirst_pos\tlast_pos\tn_sites\tvit_sites\tvit_share\tpost_sites\tpost_mean\tvit_mb\n", fh);
+  for (uint64_t i = 0; i < I; i++) {
+    const std::string id = P.ind_names.empty() ? "ind" + std::to_string(i) : P.ind_names[i];
+    for (uint64_t r = 0; r < R; r++) {
+      const nghmm_region_stat& t = reg[i * R + r];
+      const uint64_t n = end[r] - begin[r];
+      if (t.vit_sites > n || t.post_sites > n) fatal(__FUNCTION__, "a region record outside the data!");
+      fprintf(fh, "%s\t%s\t%llu\t%llu\t%llu\t%llu\t%.10g\t%llu\t%.10g\t%.10g\n", id.c_str(),
+              P.chrom_name[chrom[r]].c_str(), (unsigned long long)P.site_pos[begin[r]],
+              (unsigned long long)P.site_pos[end[r] - 1], (unsigned long long)n,
+              (unsigned long long)t.vit_sites, (double)t.vit_sites / (double)n,
+              (unsigned long long)t.post_sites, t.post_sum / (double)n, t.vit_mb);
+    }
+  }
+  if (fclose(fh) != 0) fatal(__FUNCTION__, "cannot write the region summary output file!");
+  name = P.prefix + ".ibd.sites";
+  fh = fopen(name.c_str(), "w");
+  if (!fh) fatal(__FUNCTION__, "cannot open site summary output file!");
+  setvbuf(fh, nullptr, _IOFBF, 1 << 22);
+  fputs("chr\tpos\tvit_count\tpost_count\tpost_mean\n", fh);
+  size_t c = 0;
+  for (uint64_t s = 0; s < S; s++) {
+    while (c + 1 < P.chrom_first.size() && P.chrom_first[c + 1] <= s) c++;
+    const nghmm_site_stat& t = sites[s];
+    if (t.vit_count > I || t.post_count > I) fatal(__FUNCTION__, "a site record outside the data!");
+    fprintf(fh, "%s\t%llu\t%u\t%u\t%.10g\n", P.chrom_name[c].c_str(), (unsigned long long)P.site_pos[s],
+            t.vit_count, t.post_count, t.post_sum / (double)I);
+  }
+  if (fclose(fh) != 0) fatal(__FUNCTION__, "cannot write the site summary output file!");
+}
+
 void sync_outputs(Params& P, Cohort& C, bool with_viterbi) {
   P.path.resize((size_t)P.n_ind * P.n_sites, 0);
   // indF / alpha are the cohort's on every handle; the frequencies those of its own sites
@@ -1432,6 +1507,8 @@ void parse_cmd_args(Params& P, int argc, char** argv) {  // parse_args.cpp:41-22
       {"sample_paths", required_argument, nullptr, 1012}, {"sample_seed", required_argument, nullptr, 1013},
       {"sample_keep", required_argument, nullptr, 1014},
       {"indF_se", no_argument, nullptr, 1015},        {"se_kat", no_argument, nullptr, 1016},
+      {"ibd_summary", no_argument, nullptr, 1017},    {"summary_window", required_argument, nullptr, 1018},
+      {"summary_thresh", required_argument, nullptr, 1019},
       {0, 0, 0, 0}};
   long taus_kat = 0;
   bool parse_kat = false, se_kat = false;
@@ -1471,6 +1548,12 @@ void parse_cmd_args(Params& P, int argc, char** argv) {  // parse_args.cpp:41-22
       case 1014: P.sample_keep = (unsigned)atoi(optarg); break;
       case 1015: P.indF_se = true; break;
       case 1016: se_kat = true; break;
+      case 1017: P.ibd_summary = true; break;
+      case 1018:
+        if (atoll(optarg) < 1) fatal(__FUNCTION__, "invalid --summary_window (sites per window)!");
+        P.summary_window = strtoull(optarg, nullptr, 10);
+        break;
+      case 1019: P.summary_thresh = atof(optarg); break;
       case 1000:
         if (!strcmp(optarg, "exact")) P.mode = NGHMM_MODE_EXACT;
         else if (!strcmp(optarg, "fast")) P.mode = NGHMM_MODE_FAST;
@@ -1561,6 +1644,12 @@ void parse_cmd_args(Params& P, int argc, char** argv) {  // parse_args.cpp:41-22
     fatal(__FUNCTION__, "--sample_paths: the library has no nghmm_chain_sample_paths!");
   if (P.indF_se && !nghmm_chain_obs_info)
     fatal(__FUNCTION__, "--indF_se: the library has no nghmm_chain_obs_info!");
+  if (P.ibd_summary && !nghmm_chain_ibd_summary)
+    fatal(__FUNCTION__, "--ibd_summary: the library has no nghmm_chain_ibd_summary!");
+  if (!(P.summary_thresh > 0.0 && P.summary_thresh <= 1.0))
+    fatal(__FUNCTION__, "invalid --summary_thresh (a posterior in (0, 1])!");
+  if (!P.ibd_summary && (P.summary_window || P.summary_thresh != 0.5))
+    warn(__FUNCTION__, "--summary_window and --summary_thresh are only used by --ibd_summary");
   if (P.min_iters < 1 || P.max_iters < 1 || P.min_iters >= P.max_iters)
     fatal(__FUNCTION__, "invalid number of iterations!");
   if (P.n_threads < 1) fatal(__FUNCTION__, "invalid number of threads!");
@@ -1592,8 +1681,8 @@ void parse_cmd_args(Params& P, int argc, char** argv) {  // parse_args.cpp:41-22
     gzclose(fh);
     if (P.ind_names.size() != P.n_ind)
       fatal(__FUNCTION__, "number of lines in --ind_names file is not --n_ind!");
-    if (!P.ibd_bed && !P.sample_paths && !P.indF_se)
-      warn(__FUNCTION__, "--ind_names is only used by --ibd_bed, --sample_paths and --indF_se");
+    if (!P.ibd_bed && !P.sample_paths && !P.indF_se && !P.ibd_summary)
+      warn(__FUNCTION__, "--ind_names is only used by --ibd_bed, --sample_paths, --indF_se and --ibd_summary");
   }
   P.prefix = P.out_prefix;
 }
@@ -1688,6 +1777,7 @@ void finish_run(Params& P, Cohort& C) {
   print_iter(P, C);
   if (P.sample_paths) write_samples(P, C);
   if (P.indF_se) write_indF_se(P, C);
+  if (P.ibd_summary) write_ibd_summary(P, C);
   if (P.verbose >= 2)  // (not a line of the reference's)
     fprintf(P.out, "> decoded in %.2f s, output files written in %.2f s\n", t1 - t0, omp_get_wtime() - t1);
 }
@@ -1801,6 +1891,7 @@ int main(int argc, char** argv) {
       if (r == best || P.keep_starts) {
         if (r == best && !P.keep_starts) runs[r].prefix = P.out_prefix;
         runs[r].indF_se = P.indF_se && r == best;   // the winning replicate's only
+        runs[r].ibd_summary = P.ibd_summary && r == best;
         finish_run(runs[r], cs[r]);
       }
       fclose(runs[r].out);
@@ -1813,6 +1904,10 @@ int main(int argc, char** argv) {
       if (P.ibd_bed) exts.push_back(".ibd.bed");
       if (P.sample_paths) exts.push_back(".ibd.samples");
       if (P.indF_se) exts.push_back(".indF.se");
+      if (P.ibd_summary) {
+        exts.push_back(".ibd.regions");
+        exts.push_back(".ibd.sites");
+      }
       for (unsigned k = 1; P.sample_paths && k <= P.sample_keep; k++) {
         char tag[32];
         snprintf(tag, sizeof tag, ".sample_%02u.ibd", k);

@@ -148,6 +148,9 @@ def load_library():
                                            C.POINTER(C.c_uint8)]),
         "nghmm_obs_info": (i32, [vp, dp, dp, vp]),
         "nghmm_chain_obs_info": (i32, [C.POINTER(vp), i32, dp, dp, vp]),
+        "nghmm_ibd_summary": (i32, [vp, i32, d, u64, C.POINTER(u64), C.POINTER(u64), vp, vp]),
+        "nghmm_chain_ibd_summary": (i32, [C.POINTER(vp), i32, i32, d, u64, C.POINTER(u64),
+                                          C.POINTER(u64), vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -186,6 +189,7 @@ EXPORTED_SYMBOLS = [
     "nghmm_ibd_tracts", "nghmm_chain_ibd_tracts",
     "nghmm_sample_paths", "nghmm_chain_sample_paths",
     "nghmm_obs_info", "nghmm_chain_obs_info",
+    "nghmm_ibd_summary", "nghmm_chain_ibd_summary",
 ]
 
 OBJECTIVE_FN = C.CFUNCTYPE(C.c_double, C.c_uint32, C.c_double, C.c_double, C.c_void_p)
@@ -343,6 +347,92 @@ def std_errors(info, indF, alpha):
             se_A[i] = math.sqrt(a / det)
             corr[i] = -b / math.sqrt(a * d)
     return se_F, se_A, corr
+
+
+SUMMARY_VITERBI = 1    # nghmm_ibd_summary sources, a bit mask (include/nghmm.h)
+SUMMARY_POSTERIOR = 2
+# sites per lane of the summary pass: kSummarySeg of csrc/kernels_summary.hpp.  A region is cut
+# into pieces at the multiples of this number, which fixes the order its sums are added in.
+SUMMARY_SEGMENT_SITES = 2048
+
+
+class RegionStat(C.Structure):       # nghmm_region_stat (include/nghmm.h)
+    _fields_ = [("vit_sites", C.c_uint64), ("post_sites", C.c_uint64), ("post_sum", C.c_double),
+                ("vit_mb", C.c_double)]
+
+
+class SiteStat(C.Structure):         # nghmm_site_stat (include/nghmm.h)
+    _fields_ = [("vit_count", C.c_uint32), ("post_count", C.c_uint32), ("post_sum", C.c_double)]
+
+
+REGION_STAT_DTYPE = np.dtype([("vit_sites", np.uint64), ("post_sites", np.uint64),
+                              ("post_sum", np.float64), ("vit_mb", np.float64)])
+SITE_STAT_DTYPE = np.dtype([("vit_count", np.uint32), ("post_count", np.uint32),
+                            ("post_sum", np.float64)])
+assert REGION_STAT_DTYPE.itemsize == C.sizeof(RegionStat) == 32
+assert SITE_STAT_DTYPE.itemsize == C.sizeof(SiteStat) == 16
+
+
+def _summary_what(what):
+    if isinstance(what, (int, np.integer)):
+        return int(what)
+    names = {"viterbi": SUMMARY_VITERBI, "posterior": SUMMARY_POSTERIOR}
+    mask = 0
+    for w in ((what,) if isinstance(what, str) else what):
+        if w not in names:
+            raise NgsFHMMError(-10, f"ibd_summary: unknown source {w!r} ('viterbi' or 'posterior')")
+        mask |= names[w]
+    return mask
+
+
+def _ibd_summary(call, check, n_ind, n_sites, regions, what, threshold, sites):
+    u64p = C.POINTER(C.c_uint64)
+    if regions is None:
+        reg = np.zeros((0, 2), dtype=np.uint64)
+    else:
+        reg = np.asarray(regions)
+        if reg.size == 0:
+            reg = reg.reshape(0, 2)
+        if reg.ndim != 2 or reg.shape[1] != 2 or not np.issubdtype(reg.dtype, np.integer) or \
+                (reg < 0).any():
+            raise NgsFHMMError(-10, "ibd_summary: regions is an [R][2] array of site indices "
+                                    "(begin, end)")
+        reg = reg.astype(np.uint64)
+    R = len(reg)
+    begin, end = np.ascontiguousarray(reg[:, 0]), np.ascontiguousarray(reg[:, 1])
+    region_stats = np.zeros((n_ind, R), dtype=REGION_STAT_DTYPE) if R else None
+    site_stats = np.zeros(n_sites, dtype=SITE_STAT_DTYPE) if sites else None
+    check(call(_summary_what(what), float(threshold), R,
+               begin.ctypes.data_as(u64p) if R else None, end.ctypes.data_as(u64p) if R else None,
+               C.c_void_p(region_stats.ctypes.data) if R else None,
+               C.c_void_p(site_stats.ctypes.data) if sites else None))
+    return region_stats, site_stats
+
+
+def chromosome_regions(pos_dist):
+    """One region per chromosome, [R][2] (begin, end) site indices: a chromosome starts at site 0
+    and at every site whose distance is +inf."""
+    d = np.asarray(pos_dist, dtype=np.float64)
+    if d.ndim != 1 or len(d) == 0:
+        raise NgsFHMMError(-10, "chromosome_regions: pos_dist is a non-empty [S] array")
+    start = np.isinf(d)
+    start[0] = True
+    begin = np.flatnonzero(start)
+    return np.stack([begin, np.r_[begin[1:], len(d)]], axis=1).astype(np.int64)
+
+
+def window_regions(pos_dist, n_sites):
+    """Windows of n_sites sites, [R][2] (begin, end) site indices, that restart at every
+    chromosome start: no window spans two chromosomes, and the last window of a chromosome holds
+    what is left of it."""
+    n_sites = int(n_sites)
+    if n_sites < 1:
+        raise NgsFHMMError(-10, f"window_regions: n_sites = {n_sites}")
+    out = []
+    for a, b in chromosome_regions(pos_dist):
+        begin = np.arange(a, b, n_sites)
+        out.append(np.stack([begin, np.minimum(begin + n_sites, b)], axis=1))
+    return np.concatenate(out).astype(np.int64)
 
 
 KERNEL_SLOTS = {"emission": 0, "forward": 1, "backward": 2, "lkl_batch": 3, "est_maf": 4,
@@ -733,6 +823,16 @@ class NgsFHMM:
         return _obs_info(lambda *a: self.lib.nghmm_obs_info(self._h, *a), self._check, self.n_ind,
                          indF, alpha)
 
+    def ibd_summary(self, regions=None, what=("viterbi", "posterior"), threshold=0.5, sites=True):
+        """IBD per region and per site, reduced on the device (nghmm_ibd_summary).  regions: [R][2]
+        integer array of half-open site ranges (begin, end), sorted and disjoint
+        (chromosome_regions, window_regions); what: "viterbi" (the last decode), "posterior"
+        (>= threshold) or both.  Returns (region_stats, site_stats): structured arrays [I][R] of
+        REGION_STAT_DTYPE and [S] of SITE_STAT_DTYPE; None for the one not asked for (no regions,
+        sites=False).  The fields of a source that was not asked for are 0."""
+        return _ibd_summary(lambda *a: self.lib.nghmm_ibd_summary(self._h, *a), self._check,
+                            self.n_ind, self.n_sites, regions, what, threshold, sites)
+
     # -- measurement -------------------------------------------------------
     def kernel_ms(self, name):
         """(milliseconds, launches) of a kernel family in the last call that ran it.  Fast mode's
@@ -864,6 +964,14 @@ class Chain:
         self._members_open()
         return _obs_info(lambda *a: self.lib.nghmm_chain_obs_info(self._arr, len(self.handles), *a),
                          self.handles[0]._check, self.n_ind, indF, alpha)
+
+    def ibd_summary(self, regions=None, what=("viterbi", "posterior"), threshold=0.5, sites=True):
+        """NgsFHMM.ibd_summary over the chain (nghmm_chain_ibd_summary): global site indices, a
+        region across a shard boundary is one region."""
+        self._members_open()
+        return _ibd_summary(
+            lambda *a: self.lib.nghmm_chain_ibd_summary(self._arr, len(self.handles), *a),
+            self.handles[0]._check, self.n_ind, self.n_sites, regions, what, threshold, sites)
 
     @property
     def freq(self):
