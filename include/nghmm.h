@@ -460,6 +460,60 @@ int nghmm_chain_ibd_summary(nghmm_t** hs, int n, int what, double threshold, uin
                             const uint64_t* region_begin, const uint64_t* region_end,
                             nghmm_region_stat* regions, nghmm_site_stat* sites);
 
+/* ---- pairwise IBD sharing between individuals ----
+ * How much IBD two individuals share over the sites [site_begin, site_end): three host matrices
+ * [I][I], full and symmetric, reduced on the matrix cores from the decoded path and the
+ * posteriors where the run left them.  Site indices are handle-local for one handle and global
+ * for a chain; site_begin < site_end <= S, else NGHMM_ERR_ARG.
+ *   vit_both[i][j]   the sites s of the range with path[i][s] == path[j][s] == 1, path the last
+ *                    nghmm_viterbi / nghmm_chain_viterbi decode of the loaded data
+ *                    (NGHMM_ERR_ARG if there was none since the load)
+ *   post_both[i][j]  the sites with marg_prob[i][s][1] >= threshold and
+ *                    marg_prob[j][s][1] >= threshold
+ *   post_prod[i][j]  the sum over the sites of marg_prob[i][s][1] * marg_prob[j][s][1]: the
+ *                    expected number of sites at which both are IBD (given the data the
+ *                    individuals are independent in this model)
+ * The diagonal is included: vit_both[i][i] and post_both[i][i] are i's own IBD sites,
+ * post_prod[i][i] is the sum of its squared posteriors.
+ *
+ * `what` is a bit mask of the sources: NGHMM_SHARING_VITERBI gives vit_both,
+ * NGHMM_SHARING_POSTERIOR gives post_both, post_prod or both.  The pointers of a source that is
+ * not asked for must be NULL; of a source that is, at least one is not NULL (a NULL one is not
+ * computed).  threshold in (0, 1], else -- NaN included -- NGHMM_ERR_ARG; it is only looked at
+ * when post_both is asked for.  NGHMM_ERR_ARG also for a handle without data, what == 0 or an
+ * unknown bit, and a NULL mismatch.
+ *
+ * No float atomics.  post_prod: the range is cut into K-splits -- first = site_begin rounded down
+ * to a multiple of 64, n = min(ceil((site_end - first) / 1024), max(1, min(1024, 2^28 / (8 I^2)))),
+ * len = ceil((site_end - first) / n) rounded up to a multiple of 64, split k = the sites of the
+ * range in [first + k len, first + (k + 1) len) --, a function of (I, site_begin, site_end) alone.
+ * Within a split v_mfma_f64_16x16x4_f64 accumulates four sites a step, the steps in ascending
+ * site order from the split's first site; the splits are added in site order, the first one's
+ * value first.  So the same call on the same handle gives the same bits every time, whatever
+ * `what` is and whichever other outputs are asked for.  The order of the four products inside one
+ * instruction is the hardware's: the value is defined to a bound -- within (n_sites + 1) 2^-53
+ * relative of the exact sum of its non-negative terms --, not to a bit.  The counts are exact
+ * (int32 within a split, which holds fewer than 2^31 sites, uint64 across splits).
+ * 
+ *
+ * Read-only, like nghmm_ibd_summary: an EM iteration after the call gives the bits it would have
+ * given without it.  Device scratch (kept by the handle): the splits' partial matrices, at most
+ * max(2^28, 8 I^2) bytes, one result matrix, and for post_both one byte per cell of the range
+ * (NGHMM_ERR_NOMEM when it cannot be had).
+ *
+ * Groups of individual shards (nghmm_group_*) are out of scope, as for the summary. */
+enum { NGHMM_SHARING_VITERBI = 1, NGHMM_SHARING_POSTERIOR = 2 };
+int nghmm_ibd_sharing(nghmm_t* h, int what, double threshold, uint64_t site_begin, uint64_t site_end,
+                      uint64_t* vit_both, uint64_t* post_both, double* post_prod);
+/* The same over a chain of site shards (nghmm_chain_setup, else NGHMM_ERR_ARG): every shard the
+ * range touches computes the matrices of its part of the range on its own device exactly as one
+ * handle would (a shard outside the range is not launched), and the host adds the shards'
+ * matrices in rank order, the first one's value first: the counts exactly, the doubles in that
+ * fixed order. */
+int nghmm_chain_ibd_sharing(nghmm_t** hs, int n, int what, double threshold, uint64_t site_begin,
+                            uint64_t site_end, uint64_t* vit_both, uint64_t* post_both,
+                            double* post_prod);
+
 /* ---- multi-GPU (individuals sharded over ranks) ----
  * The allele-frequency step needs every individual of a site.  A rank owns the
  * individuals [ind_begin, ind_begin + n_ind) of n_ind_total for all sites, and

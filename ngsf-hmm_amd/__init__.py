@@ -19,11 +19,13 @@ from .hmm import (NgsFHMM, NgsFHMMError, Group, Chain, MODE_EXACT, MODE_FAST, GE
                   build_library, bed_lines, TRACTS_VITERBI, TRACTS_POSTERIOR, PATH_STATS_DTYPE,
                   path_stats_summary, INFO_DTYPE, std_errors, SUMMARY_VITERBI, SUMMARY_POSTERIOR,
                   SUMMARY_SEGMENT_SITES, REGION_STAT_DTYPE, SITE_STAT_DTYPE, chromosome_regions,
-                  window_regions)
+                  window_regions, SHARING_VITERBI, SHARING_POSTERIOR, SHARING_SPLIT_SITES,
+                  sharing_splits, sharing_jaccard)
 from . import simulate
 
 __all__ = ["NgsFHMM", "NgsFHMMError", "Group", "Chain", "MODE_EXACT", "MODE_FAST", "GENO_PACKED", "LD_INTENDED", "EPROB_LD", "library_path",
            "load_library", "build_library", "simulate", "bed_lines", "TRACTS_VITERBI", "TRACTS_POSTERIOR",
            "PATH_STATS_DTYPE", "path_stats_summary", "INFO_DTYPE", "std_errors", "SUMMARY_VITERBI",
            "SUMMARY_POSTERIOR", "SUMMARY_SEGMENT_SITES", "REGION_STAT_DTYPE", "SITE_STAT_DTYPE",
-           "chromosome_regions", "window_regions"]
+           "chromosome_regions", "window_regions", "SHARING_VITERBI", "SHARING_POSTERIOR",
+           "SHARING_SPLIT_SITES", "sharing_splits", "sharing_jaccard"]

@@ -1,6 +1,6 @@
 // capi_internal.hpp -- what the translation units of the C ABI share: the handle, error plumbing,
 // and the helpers every entry point uses.  nghmm_capi.hip (handle life cycle, single-handle EM),
-// capi_load.hip (loaders), capi_output.hip (read-back and output formatting), capi_tracts.hip, capi_sample.hip, capi_info.hip, capi_summary.hip and
+// capi_load.hip (loaders), capi_output.hip (read-back and output formatting), capi_tracts.hip, capi_sample.hip, capi_info.hip, capi_summary.hip, capi_sharing.hip and
 // capi_multi.hip (individual shards, site shards, groups and chains of handles) implement include/nghmm.h.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -27,6 +27,7 @@
 #include "capi_owners.hpp"
 #include "kernels.hpp"
 #include "kernels_fast.hpp"
+#include "kernels_sharing.hpp"
 #include "kernels_summary.hpp"
 
 using namespace nghmm;
@@ -107,6 +108,9 @@ struct nghmm_handle {
   DevScratch<uint8_t> d_info;
   // region and site summaries (capi_summary.hip): piece, region and site records, the pieces
   DevScratch<uint8_t> d_summ;
+  // pairwise sharing (capi_sharing.hip): the K-splits' partial matrices, the result, the
+  // thresholded bytes
+  DevScratch<uint8_t> d_share;
   DevBuf<double> d_freq_new, d_hap;  // --freq_est 2 as intended: [S], [S][4]
 
   // multi-GPU shard
@@ -240,5 +244,13 @@ int summary_to_host(nghmm_t* h, int what, double thr, const std::vector<SummaryR
                     const uint8_t* prev_state, nghmm_region_stat* regions, nghmm_site_stat* sites);
 // out[I] (host) = the decoded state at the handle's last site
 int summary_last_state(nghmm_t* h, uint8_t* out);
+// nghmm_ibd_sharing's argument checks (capi_sharing.hip); they set the error message
+int sharing_check_args(nghmm_t* h, int what, double threshold, const void* vit_both,
+                       const void* post_both, const void* post_prod, const char* who);
+int sharing_check_range(uint64_t S, uint64_t site_begin, uint64_t site_end, const char* who);
+// the sharing matrices [I][I] of one handle over its sites [begin, end) to the host; a NULL
+// output is not computed
+int sharing_to_host(nghmm_t* h, double thr, uint64_t begin, uint64_t end, uint64_t* vit_both,
+                    uint64_t* post_both, double* post_prod);
 
 }  // namespace capi

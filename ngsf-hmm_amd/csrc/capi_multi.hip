@@ -827,3 +827,53 @@ int nghmm_chain_ibd_summary(nghmm_t** hs, int n, int what, double threshold, uin
   }
   return NGHMM_OK;
 }
+
+// Pairwise sharing over a chain: every handle the range touches computes the matrices of its part
+// of the range on its own device, and the host adds them in rank order -- the counts exactly, the
+// doubles in that fixed order.  A handle outside the range is not launched.
+int nghmm_chain_ibd_sharing(nghmm_t** hs, int n, int what, double threshold, uint64_t site_begin,
+                            uint64_t site_end, uint64_t* vit_both, uint64_t* post_both,
+                            double* post_prod) {
+  g_last_error.clear();
+  if (!is_chain(hs, n)) {
+    set_error("nghmm_chain_ibd_sharing: call nghmm_chain_setup on these handles first");
+    return NGHMM_ERR_ARG;
+  }
+  if (n == 1)
+    return nghmm_ibd_sharing(hs[0], what, threshold, site_begin, site_end, vit_both, post_both, post_prod);
+  int rc;
+  uint64_t S_tot = 0;
+  for (int r = 0; r < n; ++r) {
+    if ((rc = sharing_check_args(hs[r], what, threshold, vit_both, post_both, post_prod,
+                                 "nghmm_chain_ibd_sharing")))
+      return rc;
+    S_tot += hs[r]->S;
+  }
+  if ((rc = sharing_check_range(S_tot, site_begin, site_end, "nghmm_chain_ibd_sharing"))) return rc;
+  const size_t cells = (size_t)hs[0]->I * hs[0]->I;
+  std::vector<uint64_t> pv(vit_both ? cells : 0), pb(post_both ? cells : 0);
+  std::vector<double> pp(post_prod ? cells : 0);
+  bool first = true;
+  uint64_t base = 0;
+  for (int q = 0; q < n; ++q) {
+    nghmm_t* h = hs[q];
+    const uint64_t lo = base, hi = base + h->S;
+    base = hi;
+    if (site_end <= lo || site_begin >= hi) continue;
+    const uint64_t a = (site_begin > lo ? site_begin : lo) - lo, b = (site_end < hi ? site_end : hi) - lo;
+    if (first) {   // the first part: its value, not 0 + its value
+      if ((rc = sharing_to_host(h, threshold, a, b, vit_both, post_both, post_prod))) return rc;
+      first = false;
+      continue;
+    }
+    if ((rc = sharing_to_host(h, threshold, a, b, vit_both ? pv.data() : nullptr,
+                              post_both ? pb.data() : nullptr, post_prod ? pp.data() : nullptr)))
+      return rc;
+    for (size_t x = 0; x < cells; ++x) {
+      if (vit_both) vit_both[x] += pv[x];
+      if (post_both) post_both[x] += pb[x];
+      if (post_prod) post_prod[x] += pp[x];
+    }
+  }
+  return NGHMM_OK;
+}

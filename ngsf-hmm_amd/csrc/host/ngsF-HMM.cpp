@@ -16,7 +16,10 @@
 // conditional on the allele frequencies), --ibd_summary [--summary_window N] [--summary_thresh P]
 // (PREFIX.ibd.regions: per individual and chromosome -- or window of N sites -- the share of sites
 // that are IBD and the IBD length; PREFIX.ibd.sites: per site the number of individuals that are
-// IBD; both reduced on the device after the final decode).  --n_threads (the
+// IBD; both reduced on the device after the final decode), --ibd_sharing [--sharing_thresh P]
+// (PREFIX.ibd.sharing: per pair of individuals the sites at which both are IBD, by the decoded path
+// and by the posterior threshold P, and their expected number; genome-wide, reduced on the
+// device's matrix cores after the final decode).  --n_threads (the
 // reference's pool size) sets the host threads used for input normalisation and output
 // formatting; results do not depend on it.
 #include <fcntl.h>
@@ -54,6 +57,8 @@
 #pragma weak nghmm_chain_obs_info
 // ... and without the summary entry: --ibd_summary then stops with a message
 #pragma weak nghmm_chain_ibd_summary
+// ... and without the sharing entry: --ibd_sharing then stops with a message
+#pragma weak nghmm_chain_ibd_sharing
 
 namespace {
 
@@ -110,6 +115,10 @@ struct Params {  // ngsF-HMM.hpp:13-52
   bool ibd_summary = false;
   uint64_t summary_window = 0;
   double summary_thresh = 0.5;
+  // --ibd_sharing: PREFIX.ibd.sharing after the final decode (nghmm_chain_ibd_sharing), over all
+  // sites; --sharing_thresh P: the posterior threshold of its post_both column
+  bool ibd_sharing = false;
+  double sharing_thresh = 0.5;
   std::vector<uint64_t> site_pos;           // [S] the .pos file's integer positions
   std::vector<uint64_t> chrom_first;        // first site of every run of one chromosome name
   std::vector<std::string> chrom_name;      // ... and that name
@@ -1471,6 +1480,37 @@ void write_ibd_summary(const Params& P, Cohort& C) {
   if (fclose(fh) != 0) fatal(__FUNCTION__, "cannot write the site summary output file!");
 }
 
+// PREFIX.ibd.sharing: a header line, then per pair of individuals i <= j, in (i, j) order,
+// "IND_ID1 IND_ID2 vit_both post_both post_prod" (tab-separated; IDs as --ibd_bed names them): the
+// sites, genome-wide, at which both are IBD in the decoded path, at which both posteriors reach
+// --sharing_thresh, and the sum over the sites of the product of the two posteriors.
+void write_ibd_sharing(const Params& P, Cohort& C) {
+  if (!nghmm_chain_ibd_sharing)
+    fatal(__FUNCTION__, "--ibd_sharing: the library has no nghmm_chain_ibd_sharing!");
+  const uint64_t I = P.n_ind, S = P.n_sites;
+  std::vector<uint64_t> vit((size_t)I * I), both((size_t)I * I);
+  std::vector<double> prod((size_t)I * I);
+  check(nghmm_chain_ibd_sharing(C.hs.data(), C.n(), NGHMM_SHARING_VITERBI | NGHMM_SHARING_POSTERIOR,
+                                P.sharing_thresh, 0, S, vit.data(), both.data(), prod.data()),
+        "ibd_sharing");
+  const std::string name = P.prefix + ".ibd.sharing";
+  FILE* fh = fopen(name.c_str(), "w");
+  if (!fh) fatal(__FUNCTION__, "cannot open sharing output file!");
+  setvbuf(fh, nullptr, _IOFBF, 1 << 22);
+  fputs("ind1\tind2\tvit_both\tpost_both\tpost_prod\n", fh);
+  for (uint64_t i = 0; i < I; i++) {
+    const std::string id1 = P.ind_names.empty() ? "ind" + std::to_string(i) : P.ind_names[i];
+    for (uint64_t j = i; j < I; j++) {
+      const std::string id2 = P.ind_names.empty() ? "ind" + std::to_string(j) : P.ind_names[j];
+      const size_t x = (size_t)i * I + j;
+      if (vit[x] > S || both[x] > S) fatal(__FUNCTION__, "a sharing count outside the data!");
+      fprintf(fh, "%s\t%s\t%llu\t%llu\t%.10g\n", id1.c_str(), id2.c_str(), (unsigned long long)vit[x],
+              (unsigned long long)both[x], prod[x]);
+    }
+  }
+  if (fclose(fh) != 0) fatal(__FUNCTION__, "cannot write the sharing output file!");
+}
+
 void sync_outputs(Params& P, Cohort& C, bool with_viterbi) {
   P.path.resize((size_t)P.n_ind * P.n_sites, 0);
   // indF / alpha are the cohort's on every handle; the frequencies those of its own sites
@@ -1509,6 +1549,7 @@ void parse_cmd_args(Params& P, int argc, char** argv) {  // parse_args.cpp:41-22
       {"indF_se", no_argument, nullptr, 1015},        {"se_kat", no_argument, nullptr, 1016},
       {"ibd_summary", no_argument, nullptr, 1017},    {"summary_window", required_argument, nullptr, 1018},
       {"summary_thresh", required_argument, nullptr, 1019},
+      {"ibd_sharing", no_argument, nullptr, 1020},    {"sharing_thresh", required_argument, nullptr, 1021},
       {0, 0, 0, 0}};
   long taus_kat = 0;
   bool parse_kat = false, se_kat = false;
@@ -1554,6 +1595,8 @@ void parse_cmd_args(Params& P, int argc, char** argv) {  // parse_args.cpp:41-22
         P.summary_window = strtoull(optarg, nullptr, 10);
         break;
       case 1019: P.summary_thresh = atof(optarg); break;
+      case 1020: P.ibd_sharing = true; break;
+      case 1021: P.sharing_thresh = atof(optarg); break;
       case 1000:
         if (!strcmp(optarg, "exact")) P.mode = NGHMM_MODE_EXACT;
         else if (!strcmp(optarg, "fast")) P.mode = NGHMM_MODE_FAST;
@@ -1650,6 +1693,12 @@ void parse_cmd_args(Params& P, int argc, char** argv) {  // parse_args.cpp:41-22
     fatal(__FUNCTION__, "invalid --summary_thresh (a posterior in (0, 1])!");
   if (!P.ibd_summary && (P.summary_window || P.summary_thresh != 0.5))
     warn(__FUNCTION__, "--summary_window and --summary_thresh are only used by --ibd_summary");
+  if (P.ibd_sharing && !nghmm_chain_ibd_sharing)
+    fatal(__FUNCTION__, "--ibd_sharing: the library has no nghmm_chain_ibd_sharing!");
+  if (!(P.sharing_thresh > 0.0 && P.sharing_thresh <= 1.0))
+    fatal(__FUNCTION__, "invalid --sharing_thresh (a posterior in (0, 1])!");
+  if (!P.ibd_sharing && P.sharing_thresh != 0.5)
+    warn(__FUNCTION__, "--sharing_thresh is only used by --ibd_sharing");
   if (P.min_iters < 1 || P.max_iters < 1 || P.min_iters >= P.max_iters)
     fatal(__FUNCTION__, "invalid number of iterations!");
   if (P.n_threads < 1) fatal(__FUNCTION__, "invalid number of threads!");
@@ -1681,8 +1730,8 @@ void parse_cmd_args(Params& P, int argc, char** argv) {  // parse_args.cpp:41-22
     gzclose(fh);
     if (P.ind_names.size() != P.n_ind)
       fatal(__FUNCTION__, "number of lines in --ind_names file is not --n_ind!");
-    if (!P.ibd_bed && !P.sample_paths && !P.indF_se && !P.ibd_summary)
-      warn(__FUNCTION__, "--ind_names is only used by --ibd_bed, --sample_paths, --indF_se and --ibd_summary");
+    if (!P.ibd_bed && !P.sample_paths && !P.indF_se && !P.ibd_summary && !P.ibd_sharing)
+      warn(__FUNCTION__, "--ind_names is only used by --ibd_bed, --sample_paths, --indF_se, --ibd_summary and --ibd_sharing");
   }
   P.prefix = P.out_prefix;
 }
@@ -1778,6 +1827,7 @@ void finish_run(Params& P, Cohort& C) {
   if (P.sample_paths) write_samples(P, C);
   if (P.indF_se) write_indF_se(P, C);
   if (P.ibd_summary) write_ibd_summary(P, C);
+  if (P.ibd_sharing) write_ibd_sharing(P, C);
   if (P.verbose >= 2)  // (not a line of the reference's)
     fprintf(P.out, "> decoded in %.2f s, output files written in %.2f s\n", t1 - t0, omp_get_wtime() - t1);
 }
@@ -1892,6 +1942,7 @@ int main(int argc, char** argv) {
         if (r == best && !P.keep_starts) runs[r].prefix = P.out_prefix;
         runs[r].indF_se = P.indF_se && r == best;   // the winning replicate's only
         runs[r].ibd_summary = P.ibd_summary && r == best;
+        runs[r].ibd_sharing = P.ibd_sharing && r == best;
         finish_run(runs[r], cs[r]);
       }
       fclose(runs[r].out);
@@ -1908,6 +1959,7 @@ int main(int argc, char** argv) {
         exts.push_back(".ibd.regions");
         exts.push_back(".ibd.sites");
       }
+      if (P.ibd_sharing) exts.push_back(".ibd.sharing");
       for (unsigned k = 1; P.sample_paths && k <= P.sample_keep; k++) {
         char tag[32];
         snprintf(tag, sizeof tag, ".sample_%02u.ibd", k);

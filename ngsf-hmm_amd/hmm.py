@@ -151,6 +151,9 @@ def load_library():
         "nghmm_ibd_summary": (i32, [vp, i32, d, u64, C.POINTER(u64), C.POINTER(u64), vp, vp]),
         "nghmm_chain_ibd_summary": (i32, [C.POINTER(vp), i32, i32, d, u64, C.POINTER(u64),
                                           C.POINTER(u64), vp, vp]),
+        "nghmm_ibd_sharing": (i32, [vp, i32, d, u64, u64, C.POINTER(u64), C.POINTER(u64), dp]),
+        "nghmm_chain_ibd_sharing": (i32, [C.POINTER(vp), i32, i32, d, u64, u64, C.POINTER(u64),
+                                          C.POINTER(u64), dp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -190,6 +193,7 @@ EXPORTED_SYMBOLS = [
     "nghmm_sample_paths", "nghmm_chain_sample_paths",
     "nghmm_obs_info", "nghmm_chain_obs_info",
     "nghmm_ibd_summary", "nghmm_chain_ibd_summary",
+    "nghmm_ibd_sharing", "nghmm_chain_ibd_sharing",
 ]
 
 OBJECTIVE_FN = C.CFUNCTYPE(C.c_double, C.c_uint32, C.c_double, C.c_double, C.c_void_p)
@@ -407,6 +411,63 @@ def _ibd_summary(call, check, n_ind, n_sites, regions, what, threshold, sites):
                C.c_void_p(region_stats.ctypes.data) if R else None,
                C.c_void_p(site_stats.ctypes.data) if sites else None))
     return region_stats, site_stats
+
+
+SHARING_VITERBI = 1    # nghmm_ibd_sharing sources, a bit mask (include/nghmm.h)
+SHARING_POSTERIOR = 2
+# the least sites per K-split of the sharing kernels: kSharingSplit of csrc/kernels_sharing.hpp.
+# The splits' partial matrices are added in site order, which fixes the order of post_prod's sum.
+SHARING_SPLIT_SITES = 1024
+
+
+def sharing_splits(n_ind, site_begin, site_end):
+    """(first, length, number) of the K-splits nghmm_ibd_sharing cuts [site_begin, site_end) into:
+    sharing_plan of csrc/kernels_sharing.hpp (include/nghmm.h states the rule)."""
+    first = site_begin // 64 * 64
+    span = site_end - first
+    cap = max(1, min(1024, (1 << 28) // (8 * n_ind * n_ind)))
+    n = min(-(-span // SHARING_SPLIT_SITES), cap)
+    length = -(-(-(-span // n)) // 64) * 64
+    return first, length, -(-span // length)
+
+
+def _ibd_sharing(call, check, n_ind, n_sites, what, threshold, site_begin, site_end):
+    names = {"viterbi": SHARING_VITERBI, "posterior": SHARING_POSTERIOR,
+             "vit_both": SHARING_VITERBI, "post_both": SHARING_POSTERIOR,
+             "post_prod": SHARING_POSTERIOR}
+    outputs = {"viterbi": ("vit_both",), "posterior": ("post_both", "post_prod")}
+    mask, asked = 0, []
+    for w in ((what,) if isinstance(what, str) else what):
+        if w not in names:
+            raise NgsFHMMError(-10, f"ibd_sharing: unknown source {w!r} ('viterbi', 'posterior', or "
+                                    "one output: 'vit_both', 'post_both', 'post_prod')")
+        mask |= names[w]
+        asked += [o for o in outputs.get(w, (w,)) if o not in asked]
+    out = {o: np.zeros((n_ind, n_ind), dtype=np.float64 if o == "post_prod" else np.uint64)
+           for o in ("vit_both", "post_both", "post_prod") if o in asked}
+    u64p = C.POINTER(C.c_uint64)
+    end = n_sites if site_end is None else site_end
+    if site_begin < 0 or end < 0:
+        raise NgsFHMMError(-10, "ibd_sharing: negative site index")
+    check(call(mask, float(threshold), int(site_begin), int(end),
+               out["vit_both"].ctypes.data_as(u64p) if "vit_both" in out else None,
+               out["post_both"].ctypes.data_as(u64p) if "post_both" in out else None,
+               _dp(out["post_prod"]) if "post_prod" in out else None))
+    return out
+
+
+def sharing_jaccard(both):
+    """both[i][j] / (both[i][i] + both[j][j] - both[i][j]) of a sharing matrix (vit_both,
+    post_both): the shared IBD sites over the sites at which either is IBD; 0 where neither is
+    IBD anywhere."""
+    b = np.asarray(both, dtype=np.float64)
+    if b.ndim != 2 or b.shape[0] != b.shape[1]:
+        raise NgsFHMMError(-10, "sharing_jaccard: both is an [I][I] matrix")
+    dg = np.diag(b)
+    den = dg[:, None] + dg[None, :] - b
+    out = np.zeros_like(b)
+    np.divide(b, den, out=out, where=den != 0)
+    return out
 
 
 def chromosome_regions(pos_dist):
@@ -833,6 +894,15 @@ class NgsFHMM:
         return _ibd_summary(lambda *a: self.lib.nghmm_ibd_summary(self._h, *a), self._check,
                             self.n_ind, self.n_sites, regions, what, threshold, sites)
 
+    def ibd_sharing(self, what=("viterbi", "posterior"), threshold=0.5, site_begin=0, site_end=None):
+        """Pairwise IBD sharing over the sites [site_begin, site_end) (default: all), reduced on
+        the matrix cores (nghmm_ibd_sharing).  what: "viterbi" (vit_both, from the last decode),
+        "posterior" (post_both at >= threshold, and post_prod), or single outputs by name.
+        Returns a dict of the [I][I] arrays that were asked for: vit_both and post_both uint64,
+        post_prod float64; full, symmetric, the diagonal included."""
+        return _ibd_sharing(lambda *a: self.lib.nghmm_ibd_sharing(self._h, *a), self._check,
+                            self.n_ind, self.n_sites, what, threshold, site_begin, site_end)
+
     # -- measurement -------------------------------------------------------
     def kernel_ms(self, name):
         """(milliseconds, launches) of a kernel family in the last call that ran it.  Fast mode's
@@ -972,6 +1042,14 @@ class Chain:
         return _ibd_summary(
             lambda *a: self.lib.nghmm_chain_ibd_summary(self._arr, len(self.handles), *a),
             self.handles[0]._check, self.n_ind, self.n_sites, regions, what, threshold, sites)
+
+    def ibd_sharing(self, what=("viterbi", "posterior"), threshold=0.5, site_begin=0, site_end=None):
+        """NgsFHMM.ibd_sharing over the chain (nghmm_chain_ibd_sharing): global site indices, the
+        shards' matrices added in rank order."""
+        self._members_open()
+        return _ibd_sharing(
+            lambda *a: self.lib.nghmm_chain_ibd_sharing(self._arr, len(self.handles), *a),
+            self.handles[0]._check, self.n_ind, self.n_sites, what, threshold, site_begin, site_end)
 
     @property
     def freq(self):
