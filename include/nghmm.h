@@ -345,6 +345,69 @@ int nghmm_sample_paths(nghmm_t* h, uint64_t seed, uint32_t n_draws, nghmm_path_s
 int nghmm_chain_sample_paths(nghmm_t** hs, int n, uint64_t seed, uint32_t n_draws,
                              nghmm_path_stats* stats, uint32_t n_keep, uint8_t* paths);
 
+/* ---- support of a tract: joint posterior and log-odds of a whole run of sites ----
+ * How far to trust ONE tract: the posterior probability that individual i is IBD at EVERY site of
+ * a closed range [a, b] -- not the sum or mean of the per-site marginals (nghmm_tract.post_sum),
+ * which for strongly dependent neighbours says little about the run as a whole -- and the same for
+ * non-IBD throughout, exactly and without counting sampled paths.  (The reference has no such
+ * function; hap-ibd's LOD and bcftools roh's quality play this role elsewhere.)
+ *
+ * Definition.  At the handle's CURRENT parameters and emissions (as nghmm_viterbi,
+ * nghmm_sample_paths and nghmm_obs_info use them, not the last E-step's), with f and beta the
+ * forward and backward vectors, T_s and q as in the sampler's definition above, e_s the emissions
+ * and Z the likelihood, for k in {0, 1}:
+ *     P(z_a..b = k | y) = f_a(k) prod_{s = a+1..b} T_s(k, k) e_s(k)  beta_b(k) / Z
+ *   log_p_ibd      ln P(z_a = ... = z_b = 1 | y, theta)
+ *   log_p_non      ln P(z_a = ... = z_b = 0 | y, theta)
+ *   post_min       the smallest P(z_s = 1 | y, theta) over s in [a, b] (unsnapped: not rounded to
+ *                  0 / 1 within 1e-5 as the E-step's posteriors are)
+ *   post_min_site  the lowest site that attains it -- where the tract is most likely to be two;
+ *                  handle-local for a single handle, global for a chain
+ * At a chromosome start inside (a, b], T_s(k, k) = q_k: the quantity stays defined, and a range
+ * need not stay within a chromosome.  A state that the data exclude gives -inf, never NaN: once a
+ * factor is 0 the result is -inf, and a 0/0 factor after that counts as 0.
+ * The LOD of a tract is (log_p_ibd - log_p_non) / ln 10: the log-odds of IBD throughout against
+ * non-IBD throughout, the rest of the genome marginalised.  It is derived by the callers (the
+ * Python binding, the command line), not stored.
+ *
+ * Evaluation.  Every factor has a scale-free local form,
+ *     P(z_a..b = k | y) = P(z_a = k | y) prod_{s = a+1..b} P(z_s = k | z_{s-1} = k, y_s..),
+ *     P(z_s = k | z_{s-1} = k, y_s..) = T_s(k, k) e_s(k) beta_s(k) / beta_{s-1}(k)
+ * (the mirror image of the sampler's P(z_s | z_{s+1}, y_1..s)), in which a common factor of the two
+ * emissions cancels.  Fast mode carries the product of a range's factors inside one lane-chunk of
+ * the layout as a double in [0.5, 1) with an integer exponent, rescaled after every factor, and
+ * takes one logarithm per lane-chunk and state; exact mode adds the factors' logarithms (detmath.h)
+ * site by site.  No float atomics: a range that spans several lane-chunks or shards is the sum of
+ * its pieces in site order, the minimum is taken in site order with ties to the lowest site -- the
+ * same bits on every call, and for a record the same bits whichever other records are passed.
+ *  */
+typedef struct nghmm_tract_score {  /* 32 bytes */
+  double log_p_ibd, log_p_non, post_min;
+  uint64_t post_min_site;
+} nghmm_tract_score;
+#ifdef __cplusplus
+static_assert(sizeof(nghmm_tract_score) == 32, "nghmm_tract_score is 32 bytes");
+#endif
+/* tracts [n] (host): only ind, first_site and n_sites are read; out [n] (host), aligned with it.
+ * The ranges must be ordered by (ind, first_site) and disjoint within an individual: what
+ * nghmm_ibd_tracts returns from either source, and equally hand-made ranges such as a gene per
+ * individual.  n == 0 returns NGHMM_OK and touches nothing.  NGHMM_ERR_ARG, with a message that
+ * names the first offending record, for n_sites == 0, a range outside the data, ind >= I, wrong
+ * order or overlap; also for a NULL pointer with n > 0 and a handle without data.
+ * Self-contained like nghmm_obs_info: it refreshes stale emissions itself and leaves parameters,
+ * the posteriors of the last E-step, the Viterbi path, checkpoints and an M-step planned in
+ * advance untouched; an EM iteration after the call gives the bits it would have given without it.
+ * Device scratch grows with n and with the lane-chunks the ranges touch (NGHMM_ERR_NOMEM when it
+ * cannot be had) and is kept by the handle. */
+int nghmm_tract_support(nghmm_t* h, const nghmm_tract* tracts, uint64_t n, nghmm_tract_score* out);
+/* The same over a chain of site shards (nghmm_chain_setup, else NGHMM_ERR_ARG): global site
+ * indices; the forward vectors travel from the first shard to the last and the backward vectors
+ * from the last to the first, I x 2 doubles per boundary, as nghmm_chain_sample_paths moves its
+ * vectors and states; a range that crosses a shard boundary is the sum of its shards' parts in
+ * site order, added on the host.  (Chains of more than one handle are fast mode only.) */
+int nghmm_chain_tract_support(nghmm_t** hs, int n_handles, const nghmm_tract* tracts, uint64_t n,
+                              nghmm_tract_score* out);
+
 /* ---- observed information of indF and alpha ----
  * Per individual the log-likelihood, its gradient and its 2x2 Hessian in (F, alpha) at one point,
  * from EXACT derivatives carried through one forward pass (no finite differences): what standard

@@ -20,7 +20,7 @@ from .hmm import (NgsFHMM, NgsFHMMError, Group, Chain, MODE_EXACT, MODE_FAST, GE
                   path_stats_summary, INFO_DTYPE, std_errors, SUMMARY_VITERBI, SUMMARY_POSTERIOR,
                   SUMMARY_SEGMENT_SITES, REGION_STAT_DTYPE, SITE_STAT_DTYPE, chromosome_regions,
                   window_regions, SHARING_VITERBI, SHARING_POSTERIOR, SHARING_SPLIT_SITES,
-                  sharing_splits, sharing_jaccard)
+                  sharing_splits, sharing_jaccard, TractScore, TRACT_SCORE_DTYPE)
 from . import simulate
 
 __all__ = ["NgsFHMM", "NgsFHMMError", "Group", "Chain", "MODE_EXACT", "MODE_FAST", "GENO_PACKED", "LD_INTENDED", "EPROB_LD", "library_path",
@@ -28,4 +28,5 @@ __all__ = ["NgsFHMM", "NgsFHMMError", "Group", "Chain", "MODE_EXACT", "MODE_FAST
            "PATH_STATS_DTYPE", "path_stats_summary", "INFO_DTYPE", "std_errors", "SUMMARY_VITERBI",
            "SUMMARY_POSTERIOR", "SUMMARY_SEGMENT_SITES", "REGION_STAT_DTYPE", "SITE_STAT_DTYPE",
            "chromosome_regions", "window_regions", "SHARING_VITERBI", "SHARING_POSTERIOR",
-           "SHARING_SPLIT_SITES", "sharing_splits", "sharing_jaccard"]
+           "SHARING_SPLIT_SITES", "sharing_splits", "sharing_jaccard", "TractScore",
+           "TRACT_SCORE_DTYPE"]

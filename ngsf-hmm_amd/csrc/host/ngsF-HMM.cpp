@@ -19,7 +19,9 @@
 // IBD; both reduced on the device after the final decode), --ibd_sharing [--sharing_thresh P]
 // (PREFIX.ibd.sharing: per pair of individuals the sites at which both are IBD, by the decoded path
 // and by the posterior threshold P, and their expected number; genome-wide, reduced on the
-// device's matrix cores after the final decode).  --n_threads (the
+// device's matrix cores after the final decode), --ibd_support (PREFIX.ibd.support: per Viterbi
+// tract of PREFIX.ibd.bed the joint posterior of IBD at every one of its sites, its log-odds
+// against non-IBD throughout and its weakest site).  --n_threads (the
 // reference's pool size) sets the host threads used for input normalisation and output
 // formatting; results do not depend on it.
 #include <fcntl.h>
@@ -59,6 +61,9 @@
 #pragma weak nghmm_chain_ibd_summary
 // ... and without the sharing entry: --ibd_sharing then stops with a message
 #pragma weak nghmm_chain_ibd_sharing
+// ... and without the support entries: --ibd_support then stops with a message
+#pragma weak nghmm_tract_support
+#pragma weak nghmm_chain_tract_support
 
 namespace {
 
@@ -119,6 +124,10 @@ struct Params {  // ngsF-HMM.hpp:13-52
   // sites; --sharing_thresh P: the posterior threshold of its post_both column
   bool ibd_sharing = false;
   double sharing_thresh = 0.5;
+  // --ibd_support: PREFIX.ibd.support after the final decode -- per Viterbi tract the joint
+  // posterior of IBD throughout, its log-odds against non-IBD throughout and the weakest site
+  // (nghmm_chain_tract_support)
+  bool ibd_support = false;
   std::vector<uint64_t> site_pos;           // [S] the .pos file's integer positions
   std::vector<uint64_t> chrom_first;        // first site of every run of one chromosome name
   std::vector<std::string> chrom_name;      // ... and that name
@@ -1511,6 +1520,57 @@ void write_ibd_sharing(const Params& P, Cohort& C) {
   if (fclose(fh) != 0) fatal(__FUNCTION__, "cannot write the sharing output file!");
 }
 
+// PREFIX.ibd.support: a header line, then one line per Viterbi tract, in the order and with the
+// IDs and skips of PREFIX.ibd.bed: "chr start end ind n_sites post_mean log10_p_ibd lod post_min
+// post_min_pos" (tab-separated; start and end as in the BED file) -- the mean per-site posterior
+// of the last E-step, log10 of the joint posterior of IBD at every site of the tract at the final
+// parameters, the log-odds to base 10 of IBD throughout against non-IBD throughout, the smallest
+// per-site posterior and the position (--pos file) of the lowest site that has it.
+void write_ibd_support(const Params& P, Cohort& C) {
+  if (!nghmm_chain_tract_support || !nghmm_chain_ibd_tracts)
+    fatal(__FUNCTION__, "--ibd_support: the library has no nghmm_chain_tract_support!");
+  const uint64_t I = P.n_ind, S = P.n_sites;
+  std::vector<nghmm_tract> t;
+  if (P.decoded) {
+    uint64_t n = 0, got = 0;
+    check(nghmm_chain_ibd_tracts(C.hs.data(), C.n(), NGHMM_TRACTS_VITERBI, 0.5, 1, nullptr, 0, &n),
+          "ibd_tracts");
+    t.resize(n);
+    if (n) check(nghmm_chain_ibd_tracts(C.hs.data(), C.n(), NGHMM_TRACTS_VITERBI, 0.5, 1, t.data(), n, &got),
+                 "ibd_tracts");
+    if (got != n) fatal(__FUNCTION__, "the number of tracts changed between two calls!");
+  }
+  std::vector<nghmm_tract_score> sc(t.size());
+  check(nghmm_chain_tract_support(C.hs.data(), C.n(), t.data(), t.size(), sc.data()), "tract_support");
+  const std::string name = P.prefix + ".ibd.support";
+  FILE* fh = fopen(name.c_str(), "w");
+  if (!fh) fatal(__FUNCTION__, "cannot open tract support output file!");
+  setvbuf(fh, nullptr, _IOFBF, 1 << 22);
+  fputs("chr\tstart\tend\tind\tn_sites\tpost_mean\tlog10_p_ibd\tlod\tpost_min\tpost_min_pos\n", fh);
+  const double ln10 = 2.302585092994045684;
+  size_t c = 0;  // (as write_ibd_bed)
+  uint32_t prev_ind = UINT32_MAX;
+  for (size_t k = 0; k < t.size(); k++) {
+    const nghmm_tract& r = t[k];
+    const nghmm_tract_score& x = sc[k];
+    if (r.ind >= I || r.n_sites == 0 || r.first_site >= S || r.n_sites > S - r.first_site)
+      fatal(__FUNCTION__, "a tract outside the data!");
+    if (x.post_min_site < r.first_site || x.post_min_site >= r.first_site + r.n_sites)
+      fatal(__FUNCTION__, "a tract's weakest site outside the tract!");
+    const std::string id = P.ind_names.empty() ? "ind" + std::to_string(r.ind) : P.ind_names[r.ind];
+    if (id.empty() || id == "0") continue;
+    if (r.ind != prev_ind || P.chrom_first[c] > r.first_site) c = 0;
+    prev_ind = r.ind;
+    while (c + 1 < P.chrom_first.size() && P.chrom_first[c + 1] <= r.first_site) c++;
+    const uint64_t start = P.site_pos[r.first_site] - 1, end = P.site_pos[r.first_site + r.n_sites - 1];
+    fprintf(fh, "%s\t%llu\t%llu\t%s\t%llu\t%.10g\t%.10g\t%.10g\t%.10g\t%llu\n", P.chrom_name[c].c_str(),
+            (unsigned long long)start, (unsigned long long)end, id.c_str(), (unsigned long long)r.n_sites,
+            r.post_sum / (double)r.n_sites, x.log_p_ibd / ln10, (x.log_p_ibd - x.log_p_non) / ln10,
+            x.post_min, (unsigned long long)P.site_pos[x.post_min_site]);
+  }
+  if (fclose(fh) != 0) fatal(__FUNCTION__, "cannot write the tract support output file!");
+}
+
 void sync_outputs(Params& P, Cohort& C, bool with_viterbi) {
   P.path.resize((size_t)P.n_ind * P.n_sites, 0);
   // indF / alpha are the cohort's on every handle; the frequencies those of its own sites
@@ -1550,6 +1610,7 @@ void parse_cmd_args(Params& P, int argc, char** argv) {  // parse_args.cpp:41-22
       {"ibd_summary", no_argument, nullptr, 1017},    {"summary_window", required_argument, nullptr, 1018},
       {"summary_thresh", required_argument, nullptr, 1019},
       {"ibd_sharing", no_argument, nullptr, 1020},    {"sharing_thresh", required_argument, nullptr, 1021},
+      {"ibd_support", no_argument, nullptr, 1022},
       {0, 0, 0, 0}};
   long taus_kat = 0;
   bool parse_kat = false, se_kat = false;
@@ -1597,6 +1658,7 @@ void parse_cmd_args(Params& P, int argc, char** argv) {  // parse_args.cpp:41-22
       case 1019: P.summary_thresh = atof(optarg); break;
       case 1020: P.ibd_sharing = true; break;
       case 1021: P.sharing_thresh = atof(optarg); break;
+      case 1022: P.ibd_support = true; break;
       case 1000:
         if (!strcmp(optarg, "exact")) P.mode = NGHMM_MODE_EXACT;
         else if (!strcmp(optarg, "fast")) P.mode = NGHMM_MODE_FAST;
@@ -1699,6 +1761,8 @@ void parse_cmd_args(Params& P, int argc, char** argv) {  // parse_args.cpp:41-22
     fatal(__FUNCTION__, "invalid --sharing_thresh (a posterior in (0, 1])!");
   if (!P.ibd_sharing && P.sharing_thresh != 0.5)
     warn(__FUNCTION__, "--sharing_thresh is only used by --ibd_sharing");
+  if (P.ibd_support && (!nghmm_chain_tract_support || !nghmm_chain_ibd_tracts))
+    fatal(__FUNCTION__, "--ibd_support: the library has no nghmm_chain_tract_support!");
   if (P.min_iters < 1 || P.max_iters < 1 || P.min_iters >= P.max_iters)
     fatal(__FUNCTION__, "invalid number of iterations!");
   if (P.n_threads < 1) fatal(__FUNCTION__, "invalid number of threads!");
@@ -1730,8 +1794,8 @@ void parse_cmd_args(Params& P, int argc, char** argv) {  // parse_args.cpp:41-22
     gzclose(fh);
     if (P.ind_names.size() != P.n_ind)
       fatal(__FUNCTION__, "number of lines in --ind_names file is not --n_ind!");
-    if (!P.ibd_bed && !P.sample_paths && !P.indF_se && !P.ibd_summary && !P.ibd_sharing)
-      warn(__FUNCTION__, "--ind_names is only used by --ibd_bed, --sample_paths, --indF_se, --ibd_summary and --ibd_sharing");
+    if (!P.ibd_bed && !P.sample_paths && !P.indF_se && !P.ibd_summary && !P.ibd_sharing && !P.ibd_support)
+      warn(__FUNCTION__, "--ind_names is only used by --ibd_bed, --sample_paths, --indF_se, --ibd_summary, --ibd_sharing and --ibd_support");
   }
   P.prefix = P.out_prefix;
 }
@@ -1828,6 +1892,7 @@ void finish_run(Params& P, Cohort& C) {
   if (P.indF_se) write_indF_se(P, C);
   if (P.ibd_summary) write_ibd_summary(P, C);
   if (P.ibd_sharing) write_ibd_sharing(P, C);
+  if (P.ibd_support) write_ibd_support(P, C);
   if (P.verbose >= 2)  // (not a line of the reference's)
     fprintf(P.out, "> decoded in %.2f s, output files written in %.2f s\n", t1 - t0, omp_get_wtime() - t1);
 }
@@ -1943,6 +2008,7 @@ int main(int argc, char** argv) {
         runs[r].indF_se = P.indF_se && r == best;   // the winning replicate's only
         runs[r].ibd_summary = P.ibd_summary && r == best;
         runs[r].ibd_sharing = P.ibd_sharing && r == best;
+        runs[r].ibd_support = P.ibd_support && r == best;
         finish_run(runs[r], cs[r]);
       }
       fclose(runs[r].out);
@@ -1960,6 +2026,7 @@ int main(int argc, char** argv) {
         exts.push_back(".ibd.sites");
       }
       if (P.ibd_sharing) exts.push_back(".ibd.sharing");
+      if (P.ibd_support) exts.push_back(".ibd.support");
       for (unsigned k = 1; P.sample_paths && k <= P.sample_keep; k++) {
         char tag[32];
         snprintf(tag, sizeof tag, ".sample_%02u.ibd", k);

@@ -146,6 +146,8 @@ def load_library():
         "nghmm_sample_paths": (i32, [vp, u64, u32, vp, u32, C.POINTER(C.c_uint8)]),
         "nghmm_chain_sample_paths": (i32, [C.POINTER(vp), i32, u64, u32, vp, u32,
                                            C.POINTER(C.c_uint8)]),
+        "nghmm_tract_support": (i32, [vp, vp, u64, vp]),
+        "nghmm_chain_tract_support": (i32, [C.POINTER(vp), i32, vp, u64, vp]),
         "nghmm_obs_info": (i32, [vp, dp, dp, vp]),
         "nghmm_chain_obs_info": (i32, [C.POINTER(vp), i32, dp, dp, vp]),
         "nghmm_ibd_summary": (i32, [vp, i32, d, u64, C.POINTER(u64), C.POINTER(u64), vp, vp]),
@@ -191,6 +193,7 @@ EXPORTED_SYMBOLS = [
     "nghmm_chain_viterbi", "nghmm_alloc_host", "nghmm_free_host",
     "nghmm_ibd_tracts", "nghmm_chain_ibd_tracts",
     "nghmm_sample_paths", "nghmm_chain_sample_paths",
+    "nghmm_tract_support", "nghmm_chain_tract_support",
     "nghmm_obs_info", "nghmm_chain_obs_info",
     "nghmm_ibd_summary", "nghmm_chain_ibd_summary",
     "nghmm_ibd_sharing", "nghmm_chain_ibd_sharing",
@@ -276,6 +279,49 @@ def bed_lines(tracts, chrom_names, positions, ind_names):
         start, end = int(positions[a]) - 1, int(positions[b])
         lines.append(f"{chrom_names[a]}\t{start}\t{end}\t{ind_names[int(t['ind'])]}\t{end - start}\n")
     return "".join(lines)
+
+
+class TractScore(C.Structure):       # nghmm_tract_score (include/nghmm.h)
+    _fields_ = [("log_p_ibd", C.c_double), ("log_p_non", C.c_double), ("post_min", C.c_double),
+                ("post_min_site", C.c_uint64)]
+
+
+# tract_support's records: nghmm_tract_score and the derived LOD, (log_p_ibd - log_p_non) / ln 10
+TRACT_SCORE_DTYPE = np.dtype([("log_p_ibd", np.float64), ("log_p_non", np.float64),
+                              ("post_min", np.float64), ("post_min_site", np.uint64),
+                              ("lod", np.float64)])
+_TRACT_RAW_DTYPE = np.dtype([("first_site", np.uint64), ("n_sites", np.uint64), ("ind", np.uint32),
+                             ("reserved", np.uint32), ("post_sum", np.float64)])
+
+
+def _tract_support(call, check, tracts):
+    """tracts: ibd_tracts' structured array, or integers [n][3] of (ind, first_site, n_sites)."""
+    t = np.asarray(tracts)
+    if t.dtype.names is None:
+        if t.size == 0:
+            t = t.reshape(0, 3)
+        if t.ndim != 2 or t.shape[1] != 3 or not (np.issubdtype(t.dtype, np.integer) or t.size == 0):
+            raise NgsFHMMError(-10, "tract_support: ranges are ibd_tracts' records or integers [n][3] "
+                                    "of (ind, first_site, n_sites)")
+        if t.size and (t.min() < 0 or t[:, 0].max() >= 2 ** 32):
+            raise NgsFHMMError(-10, "tract_support: a negative value, or ind >= 2^32")
+        cols = {"ind": t[:, 0], "first_site": t[:, 1], "n_sites": t[:, 2]}
+    else:
+        cols = {f: t[f] for f in ("ind", "first_site", "n_sites")}
+    n = len(t)
+    raw = np.zeros(n, dtype=_TRACT_RAW_DTYPE)
+    for f, v in cols.items():
+        raw[f] = v
+    assert raw.itemsize == C.sizeof(Tract)
+    got = np.zeros(n, dtype=np.dtype([(f, TRACT_SCORE_DTYPE[f]) for f in TRACT_SCORE_DTYPE.names[:4]]))
+    assert got.itemsize == C.sizeof(TractScore)
+    check(call(C.c_void_p(raw.ctypes.data) if n else None, n, C.c_void_p(got.ctypes.data) if n else None))
+    out = np.empty(n, dtype=TRACT_SCORE_DTYPE)
+    for f in got.dtype.names:
+        out[f] = got[f]
+    with np.errstate(invalid="ignore"):     # (-inf) - (-inf): a range neither state can fill
+        out["lod"] = (out["log_p_ibd"] - out["log_p_non"]) / math.log(10.0)
+    return out
 
 
 # nghmm_path_stats (include/nghmm.h): one record per (draw, individual) of sample_paths
@@ -875,6 +921,16 @@ class NgsFHMM:
         return _sample_paths(lambda *a: self.lib.nghmm_sample_paths(self._h, *a), self._check,
                              self.n_ind, self.n_sites, n_draws, seed, keep)
 
+    def tract_support(self, tracts):
+        """How far to trust each of `tracts` (nghmm_tract_support): the log of the joint posterior
+        probability that the individual is IBD at every site of the range (log_p_ibd), that it is
+        non-IBD at every site (log_p_non), their log-odds to base 10 (lod), the smallest per-site
+        posterior in the range and the lowest site that has it -- at the CURRENT parameters.
+        tracts: what ibd_tracts returns, or integers [n][3] of (ind, first_site, n_sites), ordered
+        by (ind, first_site) and disjoint within an individual.  A structured array [n] of
+        TRACT_SCORE_DTYPE, aligned with the input."""
+        return _tract_support(lambda *a: self.lib.nghmm_tract_support(self._h, *a), self._check, tracts)
+
     def obs_info(self, indF=None, alpha=None):
         """Per individual the log-likelihood, its gradient and its Hessian in (indF, alpha) under
         the current emissions, from exact derivatives (nghmm_obs_info): a structured array [I] of
@@ -1028,6 +1084,14 @@ class Chain:
         return _sample_paths(
             lambda *a: self.lib.nghmm_chain_sample_paths(self._arr, len(self.handles), *a),
             self.handles[0]._check, self.n_ind, self.n_sites, n_draws, seed, keep)
+
+    def tract_support(self, tracts):
+        """NgsFHMM.tract_support over the chain (nghmm_chain_tract_support): global site indices,
+        a range across a shard boundary is one range."""
+        self._members_open()
+        return _tract_support(
+            lambda *a: self.lib.nghmm_chain_tract_support(self._arr, len(self.handles), *a),
+            self.handles[0]._check, tracts)
 
     def obs_info(self, indF=None, alpha=None):
         """NgsFHMM.obs_info over the chain (nghmm_chain_obs_info)."""
