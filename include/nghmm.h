@@ -408,6 +408,77 @@ int nghmm_tract_support(nghmm_t* h, const nghmm_tract* tracts, uint64_t n, nghmm
 int nghmm_chain_tract_support(nghmm_t** hs, int n_handles, const nghmm_tract* tracts, uint64_t n,
                               nghmm_tract_score* out);
 
+/* ---- bounds of a tract: credible intervals for its two ends ----
+ * Where a tract really starts and ends, and how likely two neighbouring calls are one tract --
+ * exactly, without keeping sampled paths.  (The reference has no such function.)
+ *
+ * Definition.  Everything uses the handle's CURRENT parameters and emissions, as
+ * nghmm_tract_support does; f, beta, T_s, q, e_s, Z as there.  Of a record only ind, first_site
+ * and n_sites are read: its CORE.  Record k has
+ *   anchor       c_k.  anchor[k] if given (it must lie inside the core); with anchor == NULL or
+ *                anchor[k] == UINT64_MAX the site of the core with the smallest P(z_s = 0 | y),
+ *                the lowest such site on ties.  P(z_s = 0 | y) is formed directly, not as
+ *                1 - P(z_s = 1 | y): inside a tract the latter saturates at 1 over many sites
+ *                while the former keeps its relative precision.  Anchors are strictly ascending
+ *                within an individual.
+ *   left_limit   max(first site of c_k's chromosome, c_{k-1}); c_{k-1} only where record k - 1
+ *                belongs to the same individual
+ *   right_limit  min(last site of c_k's chromosome, c_{k+1}), likewise.  A chromosome starts at
+ *                site 0 and at every site with distance +inf.
+ *   G(s) = P(z_s = ... = z_c = 1 | y) / P(z_c = 1 | y),   left_limit <= s <= c
+ *   H(s) = P(z_c = ... = z_s = 1 | y) / P(z_c = 1 | y),   c <= s <= right_limit;  G(c) = H(c) = 1.
+ * With the local factors of the support, g_t = T_t(1,1) e_t(1) beta_t(1) / beta_{t-1}(1):
+ *   H(s) = prod_{t = c+1..s} g_t,   G(s) = P(z_s = 1 | y) prod_{t = s+1..c} g_t / P(z_c = 1 | y).
+ * Both fall monotonically away from the anchor.  levels [n_levels], 1 <= n_levels <= 8, each in
+ * (0, 1), strictly descending:
+ *   start[k][m]  the lowest s with G(t) >= levels[m] for every t in [s, c]
+ *   end[k][m]    the highest s with H(t) >= levels[m] for every t in [c, s]
+ * Given z_c = 1, P(true start <= s) = G(s): [start(0.025), start(0.975)] is a 95 % interval of the
+ * start and start(0.5) its median; [end(0.975), end(0.025)] is the interval of the end.
+ *   post_anchor      P(z_c = 1 | y), unsnapped
+ *   log_reach_left   ln G(left_limit)
+ *   log_reach_right  ln H(right_limit)
+ * Where the limit is a neighbour's anchor, the reach is the probability that the two tracts are
+ * one run from anchor to anchor.  A level is CENSORED on a side when the answer equals the limit:
+ * when reach >= level.
+ * A factor 0 makes everything beyond it 0 (-inf); a 0/0 factor counts as 0; nothing is ever NaN.
+ * With post_anchor == 0 every start and end is the anchor and both reaches are -inf.
+ * Site indices are handle-local for one handle and global for a chain.
+ *
+ * Evaluation.  Between two consecutive anchors one set of factors serves the
+ * search to the right of the one and to the left of the other.  Fast mode: three walks of the
+ * shape of the support's -- the anchors; ln prod g per lane-chunk piece of every stretch between
+ * two limits, which the host adds in site order (and in rank order over the shards of a chain);
+ * and, knowing the value at every piece's edge, the first failing site per level from the anchor
+ * outwards.  Exact mode: the same three passes, one lane per individual in log space.  No float
+ * atomics; the same bits on every call; a record's results depend only on that record and its two
+ * neighbours in the call. */
+typedef struct nghmm_tract_bound {  /* 48 bytes */
+  uint64_t anchor, left_limit, right_limit;
+  double post_anchor, log_reach_left, log_reach_right;
+} nghmm_tract_bound;
+#ifdef __cplusplus
+static_assert(sizeof(nghmm_tract_bound) == 48, "nghmm_tract_bound is 48 bytes");
+#endif
+/* tracts [n], anchor [n] or NULL, levels [n_levels], out [n], start and end [n][n_levels] (all
+ * host).  The records are checked as nghmm_tract_support checks them, with its messages; an anchor
+ * outside its core and bad levels (count, range, order, NaN) are NGHMM_ERR_ARG too.  n == 0
+ * returns NGHMM_OK and touches nothing; a NULL pointer other than anchor with n > 0, and a handle
+ * without data, are NGHMM_ERR_ARG.  Self-contained and read-only exactly like nghmm_tract_support:
+ * it refreshes stale emissions itself and leaves parameters, posteriors, Viterbi path, checkpoints
+ * and a planned M-step untouched; an EM iteration after the call gives the bits it would have
+ * given without it.  Device scratch is kept by the handle. */
+int nghmm_tract_bounds(nghmm_t* h, const nghmm_tract* tracts, uint64_t n, const uint64_t* anchor,
+                       const double* levels, uint32_t n_levels, nghmm_tract_bound* out,
+                       uint64_t* start, uint64_t* end);
+/* The same over a chain of site shards (nghmm_chain_setup, else NGHMM_ERR_ARG): global site
+ * indices; the boundary vectors travel as in nghmm_chain_tract_support; every shard reports the
+ * pieces of a search that crosses a boundary, the host adds them in rank order and gives each
+ * shard its offsets for the locating pass.  (Chains of more than one handle are fast mode only.) */
+int nghmm_chain_tract_bounds(nghmm_t** hs, int n_handles, const nghmm_tract* tracts, uint64_t n,
+                             const uint64_t* anchor, const double* levels, uint32_t n_levels,
+                             nghmm_tract_bound* out, uint64_t* start, uint64_t* end);
+
 /* ---- observed information of indF and alpha ----
  * Per individual the log-likelihood, its gradient and its 2x2 Hessian in (F, alpha) at one point,
  * from EXACT derivatives carried through one forward pass (no finite differences): what standard

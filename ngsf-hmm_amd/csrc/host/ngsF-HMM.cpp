@@ -21,7 +21,10 @@
 // and by the posterior threshold P, and their expected number; genome-wide, reduced on the
 // device's matrix cores after the final decode), --ibd_support (PREFIX.ibd.support: per Viterbi
 // tract of PREFIX.ibd.bed the joint posterior of IBD at every one of its sites, its log-odds
-// against non-IBD throughout and its weakest site).  --n_threads (the
+// against non-IBD throughout and its weakest site), --ibd_bounds [--bounds_ci P]
+// (PREFIX.ibd.bounds: per Viterbi tract of PREFIX.ibd.bed the credible interval, of mass P, and the
+// median of its start and of its end, and the probability that it is one run with either
+// neighbour).  --n_threads (the
 // reference's pool size) sets the host threads used for input normalisation and output
 // formatting; results do not depend on it.
 #include <fcntl.h>
@@ -64,6 +67,9 @@
 // ... and without the support entries: --ibd_support then stops with a message
 #pragma weak nghmm_tract_support
 #pragma weak nghmm_chain_tract_support
+// ... and without the bounds entries: --ibd_bounds then stops with a message
+#pragma weak nghmm_tract_bounds
+#pragma weak nghmm_chain_tract_bounds
 
 namespace {
 
@@ -128,6 +134,10 @@ struct Params {  // ngsF-HMM.hpp:13-52
   // posterior of IBD throughout, its log-odds against non-IBD throughout and the weakest site
   // (nghmm_chain_tract_support)
   bool ibd_support = false;
+  // --ibd_bounds: PREFIX.ibd.bounds after the final decode -- per Viterbi tract the credible
+  // interval (--bounds_ci, its mass) and the median of either end (nghmm_chain_tract_bounds)
+  bool ibd_bounds = false;
+  double bounds_ci = 0.95;
   std::vector<uint64_t> site_pos;           // [S] the .pos file's integer positions
   std::vector<uint64_t> chrom_first;        // first site of every run of one chromosome name
   std::vector<std::string> chrom_name;      // ... and that name
@@ -1571,6 +1581,72 @@ void write_ibd_support(const Params& P, Cohort& C) {
   if (fclose(fh) != 0) fatal(__FUNCTION__, "cannot write the tract support output file!");
 }
 
+// PREFIX.ibd.bounds: a header line, then one line per Viterbi tract, in the order and with the IDs
+// and skips of PREFIX.ibd.bed: "chr start end ind anchor_pos post_anchor start_lo start_med start_hi
+// end_lo end_med end_hi left_limit_pos reach_left right_limit_pos reach_right" (tab-separated; start
+// and end as in the BED file; every *_pos, *_lo, *_med, *_hi a position of the --pos file) -- the
+// anchor (the tract's site least likely to be non-IBD) and its posterior, the interval of mass
+// --bounds_ci and the median of the tract's true start and of its true end given that the anchor
+// is IBD, and the probability that the run through the anchor reaches the limit of either search:
+// the chromosome's edge, or the neighbouring tract's anchor -- then the two tracts are one.
+void write_ibd_bounds(const Params& P, Cohort& C) {
+  if (!nghmm_chain_tract_bounds || !nghmm_chain_ibd_tracts)
+    fatal(__FUNCTION__, "--ibd_bounds: the library has no nghmm_chain_tract_bounds!");
+  const uint64_t I = P.n_ind, S = P.n_sites;
+  std::vector<nghmm_tract> t;
+  if (P.decoded) {
+    uint64_t n = 0, got = 0;
+    check(nghmm_chain_ibd_tracts(C.hs.data(), C.n(), NGHMM_TRACTS_VITERBI, 0.5, 1, nullptr, 0, &n),
+          "ibd_tracts");
+    t.resize(n);
+    if (n) check(nghmm_chain_ibd_tracts(C.hs.data(), C.n(), NGHMM_TRACTS_VITERBI, 0.5, 1, t.data(), n, &got),
+                 "ibd_tracts");
+    if (got != n) fatal(__FUNCTION__, "the number of tracts changed between two calls!");
+  }
+  const double levels[3] = {(1 + P.bounds_ci) / 2, 0.5, (1 - P.bounds_ci) / 2};
+  std::vector<nghmm_tract_bound> bd(t.size());
+  std::vector<uint64_t> st(t.size() * 3), en(t.size() * 3);
+  check(nghmm_chain_tract_bounds(C.hs.data(), C.n(), t.data(), t.size(), nullptr, levels, 3, bd.data(),
+                                 st.data(), en.data()),
+        "tract_bounds");
+  const std::string name = P.prefix + ".ibd.bounds";
+  FILE* fh = fopen(name.c_str(), "w");
+  if (!fh) fatal(__FUNCTION__, "cannot open tract bounds output file!");
+  setvbuf(fh, nullptr, _IOFBF, 1 << 22);
+  fputs("chr\tstart\tend\tind\tanchor_pos\tpost_anchor\tstart_lo\tstart_med\tstart_hi\tend_lo\tend_med\tend_hi\t"
+        "left_limit_pos\treach_left\tright_limit_pos\treach_right\n", fh);
+  size_t c = 0;  // (as write_ibd_bed)
+  uint32_t prev_ind = UINT32_MAX;
+  for (size_t k = 0; k < t.size(); k++) {
+    const nghmm_tract& r = t[k];
+    const nghmm_tract_bound& x = bd[k];
+    if (r.ind >= I || r.n_sites == 0 || r.first_site >= S || r.n_sites > S - r.first_site)
+      fatal(__FUNCTION__, "a tract outside the data!");
+    if (x.anchor < r.first_site || x.anchor >= r.first_site + r.n_sites)
+      fatal(__FUNCTION__, "a tract's anchor outside the tract!");
+    if (x.left_limit > x.anchor || x.right_limit < x.anchor || x.right_limit >= S)
+      fatal(__FUNCTION__, "a tract's limits do not enclose its anchor!");
+    for (int m = 0; m < 3; m++)
+      if (st[k * 3 + m] < x.left_limit || st[k * 3 + m] > x.anchor || en[k * 3 + m] < x.anchor ||
+          en[k * 3 + m] > x.right_limit)
+        fatal(__FUNCTION__, "a tract's bound outside its limits!");
+    const std::string id = P.ind_names.empty() ? "ind" + std::to_string(r.ind) : P.ind_names[r.ind];
+    if (id.empty() || id == "0") continue;
+    if (r.ind != prev_ind || P.chrom_first[c] > r.first_site) c = 0;
+    prev_ind = r.ind;
+    while (c + 1 < P.chrom_first.size() && P.chrom_first[c + 1] <= r.first_site) c++;
+    const uint64_t start = P.site_pos[r.first_site] - 1, end = P.site_pos[r.first_site + r.n_sites - 1];
+    auto at = [&](uint64_t s) { return (unsigned long long)P.site_pos[s]; };
+    // start: level (1 + P) / 2 gives the upper end of the interval, (1 - P) / 2 the lower; end: the reverse
+    fprintf(fh, "%s\t%llu\t%llu\t%s\t%llu\t%.10g\t%llu\t%llu\t%llu\t%llu\t%llu\t%llu\t%llu\t%.10g\t%llu\t%.10g\n",
+            P.chrom_name[c].c_str(), (unsigned long long)start, (unsigned long long)end, id.c_str(),
+            at(x.anchor), x.post_anchor, at(st[k * 3 + 2]), at(st[k * 3 + 1]), at(st[k * 3]), at(en[k * 3]),
+            at(en[k * 3 + 1]), at(en[k * 3 + 2]), at(x.left_limit), exp(x.log_reach_left), at(x.right_limit),
+            exp(x.log_reach_right));
+  }
+  if (fclose(fh) != 0) fatal(__FUNCTION__, "cannot write the tract bounds output file!");
+}
+
 void sync_outputs(Params& P, Cohort& C, bool with_viterbi) {
   P.path.resize((size_t)P.n_ind * P.n_sites, 0);
   // indF / alpha are the cohort's on every handle; the frequencies those of its own sites
@@ -1611,6 +1687,7 @@ void parse_cmd_args(Params& P, int argc, char** argv) {  // parse_args.cpp:41-22
       {"summary_thresh", required_argument, nullptr, 1019},
       {"ibd_sharing", no_argument, nullptr, 1020},    {"sharing_thresh", required_argument, nullptr, 1021},
       {"ibd_support", no_argument, nullptr, 1022},
+      {"ibd_bounds", no_argument, nullptr, 1023},     {"bounds_ci", required_argument, nullptr, 1024},
       {0, 0, 0, 0}};
   long taus_kat = 0;
   bool parse_kat = false, se_kat = false;
@@ -1659,6 +1736,8 @@ void parse_cmd_args(Params& P, int argc, char** argv) {  // parse_args.cpp:41-22
       case 1020: P.ibd_sharing = true; break;
       case 1021: P.sharing_thresh = atof(optarg); break;
       case 1022: P.ibd_support = true; break;
+      case 1023: P.ibd_bounds = true; break;
+      case 1024: P.bounds_ci = atof(optarg); break;
       case 1000:
         if (!strcmp(optarg, "exact")) P.mode = NGHMM_MODE_EXACT;
         else if (!strcmp(optarg, "fast")) P.mode = NGHMM_MODE_FAST;
@@ -1763,6 +1842,11 @@ void parse_cmd_args(Params& P, int argc, char** argv) {  // parse_args.cpp:41-22
     warn(__FUNCTION__, "--sharing_thresh is only used by --ibd_sharing");
   if (P.ibd_support && (!nghmm_chain_tract_support || !nghmm_chain_ibd_tracts))
     fatal(__FUNCTION__, "--ibd_support: the library has no nghmm_chain_tract_support!");
+  if (P.ibd_bounds && (!nghmm_chain_tract_bounds || !nghmm_chain_ibd_tracts))
+    fatal(__FUNCTION__, "--ibd_bounds: the library has no nghmm_chain_tract_bounds!");
+  if (P.ibd_bounds && !(P.bounds_ci > 0 && P.bounds_ci < 1))
+    fatal(__FUNCTION__, "--bounds_ci must be inside (0, 1)!");
+  if (!P.ibd_bounds && P.bounds_ci != 0.95) warn(__FUNCTION__, "--bounds_ci is only used by --ibd_bounds");
   if (P.min_iters < 1 || P.max_iters < 1 || P.min_iters >= P.max_iters)
     fatal(__FUNCTION__, "invalid number of iterations!");
   if (P.n_threads < 1) fatal(__FUNCTION__, "invalid number of threads!");
@@ -1794,8 +1878,9 @@ void parse_cmd_args(Params& P, int argc, char** argv) {  // parse_args.cpp:41-22
     gzclose(fh);
     if (P.ind_names.size() != P.n_ind)
       fatal(__FUNCTION__, "number of lines in --ind_names file is not --n_ind!");
-    if (!P.ibd_bed && !P.sample_paths && !P.indF_se && !P.ibd_summary && !P.ibd_sharing && !P.ibd_support)
-      warn(__FUNCTION__, "--ind_names is only used by --ibd_bed, --sample_paths, --indF_se, --ibd_summary, --ibd_sharing and --ibd_support");
+    if (!P.ibd_bed && !P.sample_paths && !P.indF_se && !P.ibd_summary && !P.ibd_sharing && !P.ibd_support &&
+        !P.ibd_bounds)
+      warn(__FUNCTION__, "--ind_names is only used by --ibd_bed, --sample_paths, --indF_se, --ibd_summary, --ibd_sharing, --ibd_support and --ibd_bounds");
   }
   P.prefix = P.out_prefix;
 }
@@ -1893,6 +1978,7 @@ void finish_run(Params& P, Cohort& C) {
   if (P.ibd_summary) write_ibd_summary(P, C);
   if (P.ibd_sharing) write_ibd_sharing(P, C);
   if (P.ibd_support) write_ibd_support(P, C);
+  if (P.ibd_bounds) write_ibd_bounds(P, C);
   if (P.verbose >= 2)  // (not a line of the reference's)
     fprintf(P.out, "> decoded in %.2f s, output files written in %.2f s\n", t1 - t0, omp_get_wtime() - t1);
 }
@@ -2009,6 +2095,7 @@ int main(int argc, char** argv) {
         runs[r].ibd_summary = P.ibd_summary && r == best;
         runs[r].ibd_sharing = P.ibd_sharing && r == best;
         runs[r].ibd_support = P.ibd_support && r == best;
+        runs[r].ibd_bounds = P.ibd_bounds && r == best;
         finish_run(runs[r], cs[r]);
       }
       fclose(runs[r].out);
@@ -2027,6 +2114,7 @@ int main(int argc, char** argv) {
       }
       if (P.ibd_sharing) exts.push_back(".ibd.sharing");
       if (P.ibd_support) exts.push_back(".ibd.support");
+      if (P.ibd_bounds) exts.push_back(".ibd.bounds");
       for (unsigned k = 1; P.sample_paths && k <= P.sample_keep; k++) {
         char tag[32];
         snprintf(tag, sizeof tag, ".sample_%02u.ibd", k);

@@ -148,6 +148,8 @@ def load_library():
                                            C.POINTER(C.c_uint8)]),
         "nghmm_tract_support": (i32, [vp, vp, u64, vp]),
         "nghmm_chain_tract_support": (i32, [C.POINTER(vp), i32, vp, u64, vp]),
+        "nghmm_tract_bounds": (i32, [vp, vp, u64, vp, dp, u32, vp, vp, vp]),
+        "nghmm_chain_tract_bounds": (i32, [C.POINTER(vp), i32, vp, u64, vp, dp, u32, vp, vp, vp]),
         "nghmm_obs_info": (i32, [vp, dp, dp, vp]),
         "nghmm_chain_obs_info": (i32, [C.POINTER(vp), i32, dp, dp, vp]),
         "nghmm_ibd_summary": (i32, [vp, i32, d, u64, C.POINTER(u64), C.POINTER(u64), vp, vp]),
@@ -194,6 +196,7 @@ EXPORTED_SYMBOLS = [
     "nghmm_ibd_tracts", "nghmm_chain_ibd_tracts",
     "nghmm_sample_paths", "nghmm_chain_sample_paths",
     "nghmm_tract_support", "nghmm_chain_tract_support",
+    "nghmm_tract_bounds", "nghmm_chain_tract_bounds",
     "nghmm_obs_info", "nghmm_chain_obs_info",
     "nghmm_ibd_summary", "nghmm_chain_ibd_summary",
     "nghmm_ibd_sharing", "nghmm_chain_ibd_sharing",
@@ -294,25 +297,31 @@ _TRACT_RAW_DTYPE = np.dtype([("first_site", np.uint64), ("n_sites", np.uint64), 
                              ("reserved", np.uint32), ("post_sum", np.float64)])
 
 
-def _tract_support(call, check, tracts):
-    """tracts: ibd_tracts' structured array, or integers [n][3] of (ind, first_site, n_sites)."""
+def _tract_records(tracts, who):
+    """tracts: ibd_tracts' structured array, or integers [n][3] of (ind, first_site, n_sites);
+    as nghmm_tract records."""
     t = np.asarray(tracts)
     if t.dtype.names is None:
         if t.size == 0:
             t = t.reshape(0, 3)
         if t.ndim != 2 or t.shape[1] != 3 or not (np.issubdtype(t.dtype, np.integer) or t.size == 0):
-            raise NgsFHMMError(-10, "tract_support: ranges are ibd_tracts' records or integers [n][3] "
+            raise NgsFHMMError(-10, f"{who}: ranges are ibd_tracts' records or integers [n][3] "
                                     "of (ind, first_site, n_sites)")
         if t.size and (t.min() < 0 or t[:, 0].max() >= 2 ** 32):
-            raise NgsFHMMError(-10, "tract_support: a negative value, or ind >= 2^32")
+            raise NgsFHMMError(-10, f"{who}: a negative value, or ind >= 2^32")
         cols = {"ind": t[:, 0], "first_site": t[:, 1], "n_sites": t[:, 2]}
     else:
         cols = {f: t[f] for f in ("ind", "first_site", "n_sites")}
-    n = len(t)
-    raw = np.zeros(n, dtype=_TRACT_RAW_DTYPE)
+    raw = np.zeros(len(t), dtype=_TRACT_RAW_DTYPE)
     for f, v in cols.items():
         raw[f] = v
     assert raw.itemsize == C.sizeof(Tract)
+    return raw
+
+
+def _tract_support(call, check, tracts):
+    raw = _tract_records(tracts, "tract_support")
+    n = len(raw)
     got = np.zeros(n, dtype=np.dtype([(f, TRACT_SCORE_DTYPE[f]) for f in TRACT_SCORE_DTYPE.names[:4]]))
     assert got.itemsize == C.sizeof(TractScore)
     check(call(C.c_void_p(raw.ctypes.data) if n else None, n, C.c_void_p(got.ctypes.data) if n else None))
@@ -322,6 +331,49 @@ def _tract_support(call, check, tracts):
     with np.errstate(invalid="ignore"):     # (-inf) - (-inf): a range neither state can fill
         out["lod"] = (out["log_p_ibd"] - out["log_p_non"]) / math.log(10.0)
     return out
+
+
+class TractBound(C.Structure):       # nghmm_tract_bound (include/nghmm.h)
+    _fields_ = [("anchor", C.c_uint64), ("left_limit", C.c_uint64), ("right_limit", C.c_uint64),
+                ("post_anchor", C.c_double), ("log_reach_left", C.c_double),
+                ("log_reach_right", C.c_double)]
+
+
+# tract_bounds' records: nghmm_tract_bound and the two reaches themselves, exp of their logarithms
+TRACT_BOUND_DTYPE = np.dtype([("anchor", np.uint64), ("left_limit", np.uint64),
+                              ("right_limit", np.uint64), ("post_anchor", np.float64),
+                              ("log_reach_left", np.float64), ("log_reach_right", np.float64),
+                              ("reach_left", np.float64), ("reach_right", np.float64)])
+NO_ANCHOR = 2 ** 64 - 1     # an anchor the call resolves itself (UINT64_MAX)
+
+
+def _tract_bounds(call, check, tracts, anchors, levels):
+    raw = _tract_records(tracts, "tract_bounds")
+    n = len(raw)
+    lv = np.ascontiguousarray(np.atleast_1d(np.asarray(levels, dtype=np.float64)))
+    if lv.ndim != 1:
+        raise NgsFHMMError(-10, "tract_bounds: levels is a sequence of probabilities")
+    m = len(lv)
+    anc = None
+    if anchors is not None:
+        a = np.asarray(anchors)
+        if a.shape != (n,) or not (np.issubdtype(a.dtype, np.integer) or a.size == 0):
+            raise NgsFHMMError(-10, "tract_bounds: anchors are integers [n], one per record")
+        if a.size and a.min() < 0:
+            raise NgsFHMMError(-10, "tract_bounds: a negative anchor")
+        anc = np.ascontiguousarray(a, dtype=np.uint64)
+    got = np.zeros(n, dtype=np.dtype([(f, TRACT_BOUND_DTYPE[f]) for f in TRACT_BOUND_DTYPE.names[:6]]))
+    assert got.itemsize == C.sizeof(TractBound)
+    start = np.zeros((n, m), dtype=np.uint64)
+    end = np.zeros((n, m), dtype=np.uint64)
+    ptr = lambda x: C.c_void_p(x.ctypes.data) if x is not None and x.size else None
+    check(call(ptr(raw), n, ptr(anc), _dp(lv) if m else None, m, ptr(got), ptr(start), ptr(end)))
+    out = np.empty(n, dtype=TRACT_BOUND_DTYPE)
+    for f in got.dtype.names:
+        out[f] = got[f]
+    out["reach_left"] = np.exp(out["log_reach_left"])
+    out["reach_right"] = np.exp(out["log_reach_right"])
+    return out, start, end
 
 
 # nghmm_path_stats (include/nghmm.h): one record per (draw, individual) of sample_paths
@@ -931,6 +983,22 @@ class NgsFHMM:
         TRACT_SCORE_DTYPE, aligned with the input."""
         return _tract_support(lambda *a: self.lib.nghmm_tract_support(self._h, *a), self._check, tracts)
 
+    def tract_bounds(self, tracts, anchors=None, levels=(0.975, 0.5, 0.025)):
+        """Where each of `tracts` really starts and ends (nghmm_tract_bounds), at the CURRENT
+        parameters.  Given that the individual is IBD at a record's anchor (anchors[k], or with
+        anchors None / NO_ANCHOR the site of the range least likely to be non-IBD), G(s) is the
+        probability that the IBD run through the anchor reaches down to at least site s and H(s)
+        that it reaches up to s.  Returns (bounds, start, end): bounds, a structured array [n] of
+        TRACT_BOUND_DTYPE (anchor, the limits of the two searches -- the chromosome's edge or the
+        neighbouring record's anchor --, post_anchor, and the reach to either limit: towards a
+        neighbour's anchor the probability that the two tracts are one); start / end, uint64
+        [n][len(levels)]: the lowest site with G >= level and the highest with H >= level, so that
+        start[:, 2] .. start[:, 0] with the default levels is the 95 % interval of the start with
+        its median in between, and end[:, 0] .. end[:, 2] that of the end.  levels: at most 8, in
+        (0, 1), strictly descending.  tracts as for tract_support."""
+        return _tract_bounds(lambda *a: self.lib.nghmm_tract_bounds(self._h, *a), self._check, tracts,
+                             anchors, levels)
+
     def obs_info(self, indF=None, alpha=None):
         """Per individual the log-likelihood, its gradient and its Hessian in (indF, alpha) under
         the current emissions, from exact derivatives (nghmm_obs_info): a structured array [I] of
@@ -1092,6 +1160,14 @@ class Chain:
         return _tract_support(
             lambda *a: self.lib.nghmm_chain_tract_support(self._arr, len(self.handles), *a),
             self.handles[0]._check, tracts)
+
+    def tract_bounds(self, tracts, anchors=None, levels=(0.975, 0.5, 0.025)):
+        """NgsFHMM.tract_bounds over the chain (nghmm_chain_tract_bounds): global site indices, a
+        search across a shard boundary is one search."""
+        self._members_open()
+        return _tract_bounds(
+            lambda *a: self.lib.nghmm_chain_tract_bounds(self._arr, len(self.handles), *a),
+            self.handles[0]._check, tracts, anchors, levels)
 
     def obs_info(self, indF=None, alpha=None):
         """NgsFHMM.obs_info over the chain (nghmm_chain_obs_info)."""
