@@ -479,6 +479,99 @@ int nghmm_chain_tract_bounds(nghmm_t** hs, int n_handles, const nghmm_tract* tra
                              const uint64_t* anchor, const double* levels, uint32_t n_levels,
                              nghmm_tract_bound* out, uint64_t* start, uint64_t* end);
 
+/* ---- per-site likelihood in the allele frequency: score, information and curve ----
+ * What the data of the whole cohort say about ONE site's allele frequency f_s, with indF, alpha
+ * and every other site's frequency held at the handle's current values: the uncertainty of
+ * freq[s], a per-site fit score, and how far est_maf's fixed point (gen_func.cpp:974-1009, a
+ * mean-field step that feeds the posterior -- which already contains the site's own data -- in as
+ * a fractional F) is from a stationary point of the likelihood the rest of the program optimises.
+ * (The reference has no such function.)
+ *
+ * Definition.  For one individual the data of site s enter the likelihood Z_i only through the two
+ * emissions of that site, and Z_i is linear in them:
+ *     Z_i = C_i [ (1 - c_is) e0_is(f_s) + c_is e1_is(f_s) ],
+ *     c_is = P(z_is = 1 | all data of individual i except site s's), the CAVITY probability:
+ *            (f_{s-1} T_s)(k) beta_s(k), k = 0, 1, normalised -- the forward prediction before the
+ *            emission of s is applied (at site 0 and at a chromosome start: the stationary vector
+ *            (1 - F_i, F_i)), times the backward vector;
+ *     e0 = p0 (1 - f)^2 + 2 p1 f (1 - f) + p2 f^2,   e1 = p0 (1 - f) + p2 f,   p_g = exp(gl_g)
+ * (calc_emission, HMM.cpp:144-154, with calc_HWE's F = 0 and F = 1: the heterozygote has prior 0
+ * under IBD).  c_is and C_i do not depend on f_s, so up to a constant the log-likelihood of the
+ * cohort as a function of f_s alone is EXACTLY
+ *     l_s(f) = sum_i ln[ (1 - c_is) e0_is(f) + c_is e1_is(f) ],
+ * every term the logarithm of a quadratic in f.  Everything is evaluated at the handle's CURRENT
+ * indF, alpha and freq (as nghmm_tract_support does, with walks of its own): the posteriors of the
+ * last E-step will not do -- they are snapped to 0 / 1 within 1e-5 (EM.cpp:184) and one parameter
+ * update old -- and are not looked at, nor is the decoded path.
+ *
+ *   cavity [I][S]   c_is.  The two weights (1 - c) and c are each formed from their own
+ *                   unnormalised product, never as 1 - c, so either end keeps its relative
+ *                   precision; the sums below use those two weights.
+ *   stats [S]       freq   the frequency the record was evaluated at, freq[s]
+ *                   ll     l_s(freq): the leave-one-site-out predictive log-likelihood of the
+ *                          site's data, a per-site fit score
+ *                   score  dl_s/df at freq = sum_i u_i,
+ *                          u_i = [(1 - c) e0' + c e1'] / [(1 - c) e0 + c e1]
+ *                   info   -d2l_s/df2 at freq = sum_i (u_i^2 - (1 - c) e0'' / [(1 - c) e0 + c e1])
+ *                          (e1'' = 0)
+ *   curve [S][n_levels]  curve[s][k] = l_s(levels[k]) - l_s(freq[s]), formed as the sum over i of
+ *                   ln(ratio of the two brackets), not as a difference of two sums.
+ *                   0 <= n_levels <= 8, every level in [0, 1].  Levels 0 and 1 are legal: there
+ *                   e0 = e1 = p0 (resp. p2), so -2 curve is a likelihood-ratio statistic against
+ *                   a monomorphic site.
+ * 1 / sqrt(info) is a standard error of freq[s] CONDITIONAL on indF, alpha and the other sites'
+ * frequencies (the cross terms are not formed: if anything it is too small), and only where
+ * info > 0 and 0 < freq < 1.  score at est_maf's frequency need not be 0, for the reason above.
+ *
+ * Zero likelihoods (called genotypes at level 0 or 1): an individual whose bracket is 0 at a level
+ * makes that curve entry -inf; if it is 0 at the current frequency, ll = -inf and score, info and
+ * the site's curve are NaN.  Otherwise nothing is NaN.
+ *
+ * Evaluation.  The results are the same bits however the sites are cut into
+ * shards, so the vectors cannot come from the E-step's lane-chunk operators and checkpoints (a
+ * product of operators is rounded along its grouping, which belongs to a handle's layout).  Fast
+ * mode: two plain vector recursions in linear space over the likelihoods and the frequencies, one
+ * site after the other, one lane per individual and chromosome -- a chromosome's first site
+ * restarts both exactly: its prediction is defined as (1 - F, F), the backward vector in front of
+ * it as (1, 1), the scale of a vector being free --; the backward one leaves the two weights of
+ * every cell.  Exact mode: one lane per individual in log space (detmath.h), both vectors
+ * normalised at every site.  Then a site pass over the weights and the likelihoods.  No float
+ * atomics: a site's sums run over the individuals in blocks of 64; within a block (filled up
+ * with zeros) the 64 values are added as a butterfly -- x_i += x_{i ^ 32}, then ^ 16, 8, 4, 2, 1 --;
+ * the blocks are added in order, the first one's value first (nghmm_ibd_summary's rule for
+ * post_sum).  The same bits on every call, whichever outputs are asked for; a site's result
+ * depends only on that site's cells and the cavity. */
+typedef struct nghmm_freq_stat {  /* 32 bytes; one per site */
+  double freq, ll, score, info;
+} nghmm_freq_stat;
+#ifdef __cplusplus
+static_assert(sizeof(nghmm_freq_stat) == 32, "nghmm_freq_stat is 32 bytes");
+#endif
+/* levels [n_levels], stats [S], curve [S][n_levels], cavity [I][S] (all host).  stats and cavity
+ * may be NULL; curve is NULL iff n_levels == 0 (levels is not read then); at least one of the three
+ * outputs is not NULL.  NGHMM_ERR_ARG, with a message, for n_levels > 8, a level outside [0, 1]
+ * (NaN included), a NULL mismatch, all outputs NULL, and a handle without data.
+ * Self-contained and read-only: parameters, emissions, the posteriors of the last E-step, the
+ * Viterbi path, checkpoints and an M-step planned in advance stay as they are; an EM iteration
+ * after the call gives the bits it would have given without it.  Both modes form the emissions
+ * they need from the likelihoods and the current frequencies themselves, so frequencies installed
+ * with nghmm_set_params count at once, with or without nghmm_emission, and the stored emissions
+ * are neither read nor written.  A NaN in the walks raises the invalid-likelihood error of the
+ * E-step (an individual whose likelihood is 0 on a chromosome of more than one site gives one); a
+ * NaN that arises in a site's sums stays in the record.  Device scratch, kept by the handle: 16 bytes per cell for the two weights, 8
+ * more when cavity is asked for, and the records (NGHMM_ERR_NOMEM when it cannot be had). */
+int nghmm_freq_info(nghmm_t* h, uint32_t n_levels, const double* levels, nghmm_freq_stat* stats,
+                    double* curve, double* cavity);
+/* The same over a chain of site shards (nghmm_chain_setup, else NGHMM_ERR_ARG): global site order,
+ * the outputs are the concatenation of the shards' (cavity [I][all sites]).  The forward vectors
+ * travel from the first shard to the last and the backward vectors from the last to the first,
+ * I x 2 doubles per boundary, the way nghmm_chain_tract_support moves its vectors; a shard goes on
+ * from them with the single handle's own operations, so the bytes equal the single handle's.
+ * (Chains of more than one handle are fast mode only.)  Groups of individual shards
+ * (nghmm_group_*) are out of scope, as for nghmm_ibd_summary. */
+int nghmm_chain_freq_info(nghmm_t** hs, int n_handles, uint32_t n_levels, const double* levels,
+                          nghmm_freq_stat* stats, double* curve, double* cavity);
+
 /* ---- observed information of indF and alpha ----
  * Per individual the log-likelihood, its gradient and its 2x2 Hessian in (F, alpha) at one point,
  * from EXACT derivatives carried through one forward pass (no finite differences): what standard

@@ -1,6 +1,6 @@
 // capi_internal.hpp -- what the translation units of the C ABI share: the handle, error plumbing,
 // and the helpers every entry point uses.  nghmm_capi.hip (handle life cycle, single-handle EM),
-// capi_load.hip (loaders), capi_output.hip (read-back and output formatting), capi_tracts.hip, capi_sample.hip, capi_info.hip, capi_summary.hip, capi_sharing.hip, capi_support.hip, capi_bounds.hip and
+// capi_load.hip (loaders), capi_output.hip (read-back and output formatting), capi_tracts.hip, capi_sample.hip, capi_info.hip, capi_summary.hip, capi_sharing.hip, capi_support.hip, capi_bounds.hip, capi_freqinfo.hip and
 // capi_multi.hip (individual shards, site shards, groups and chains of handles) implement include/nghmm.h.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -115,6 +115,9 @@ struct nghmm_handle {
   DevScratch<uint8_t> d_supp;
   // tract bounds (capi_bounds.hip): the boundary vectors, then each pass's ranges, offsets and pieces
   DevScratch<uint8_t> d_bnd;
+  // per-site likelihood in the frequency (capi_freqinfo.hip): the boundary vectors, the cavity
+  // weights of every cell, the site records and the curve
+  DevScratch<uint8_t> d_finfo;
   DevBuf<double> d_freq_new, d_hap;  // --freq_est 2 as intended: [S], [S][4]
 
   // multi-GPU shard

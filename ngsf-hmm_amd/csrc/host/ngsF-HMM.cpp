@@ -24,8 +24,10 @@
 // against non-IBD throughout and its weakest site), --ibd_bounds [--bounds_ci P]
 // (PREFIX.ibd.bounds: per Viterbi tract of PREFIX.ibd.bed the credible interval, of mass P, and the
 // median of its start and of its end, and the probability that it is one run with either
-// neighbour).  --n_threads (the
-// reference's pool size) sets the host threads used for input normalisation and output
+// neighbour), --freq_info [--freq_levels a,b,...] (PREFIX.freq.info: per site the log-likelihood of
+// the cohort in that site's allele frequency at the final parameters -- its value, score,
+// information and the standard error made of it, and its change at every level; default level 0).
+// --n_threads (the reference's pool size) sets the host threads used for input normalisation and output
 // formatting; results do not depend on it.
 #include <fcntl.h>
 #include <getopt.h>
@@ -70,6 +72,8 @@
 // ... and without the bounds entries: --ibd_bounds then stops with a message
 #pragma weak nghmm_tract_bounds
 #pragma weak nghmm_chain_tract_bounds
+// ... and without the frequency-information entry: --freq_info then stops with a message
+#pragma weak nghmm_chain_freq_info
 
 namespace {
 
@@ -138,6 +142,12 @@ struct Params {  // ngsF-HMM.hpp:13-52
   // interval (--bounds_ci, its mass) and the median of either end (nghmm_chain_tract_bounds)
   bool ibd_bounds = false;
   double bounds_ci = 0.95;
+  // --freq_info: PREFIX.freq.info after the final decode and every other output -- per site the
+  // likelihood in its allele frequency (nghmm_chain_freq_info); --freq_levels a,b,...: the levels
+  // of its dll_ columns (at most 8, in [0, 1]; default 0)
+  bool freq_info = false;
+  std::vector<double> freq_levels = {0.0};
+  bool freq_levels_given = false;
   std::vector<uint64_t> site_pos;           // [S] the .pos file's integer positions
   std::vector<uint64_t> chrom_first;        // first site of every run of one chromosome name
   std::vector<std::string> chrom_name;      // ... and that name
@@ -1647,6 +1657,51 @@ void write_ibd_bounds(const Params& P, Cohort& C) {
   if (fclose(fh) != 0) fatal(__FUNCTION__, "cannot write the tract bounds output file!");
 }
 
+// a double of PREFIX.freq.info: %.10g, NaN as NA, -inf as -inf
+void put_g10(FILE* fh, double v) {
+  if (v != v) fputs("\tNA", fh);
+  else if (std::isinf(v)) fputs(v < 0 ? "\t-inf" : "\tinf", fh);
+  else fprintf(fh, "\t%.10g", v);
+}
+
+// PREFIX.freq.info: a header line, then per site "chr pos freq se ll score info" and one dll_<level>
+// column per level (tab-separated): the frequency the run ended with, the standard error
+// 1 / sqrt(info) -- conditional on indF, alpha and the other sites' frequencies; NA unless info > 0
+// and 0 < freq < 1 --, the log-likelihood of the cohort in that site's frequency alone at freq, its
+// first derivative and minus its second there, and its value at every level minus the one at freq.
+void write_freq_info(const Params& P, Cohort& C) {
+  if (!nghmm_chain_freq_info) fatal(__FUNCTION__, "--freq_info: the library has no nghmm_chain_freq_info!");
+  const uint64_t S = P.n_sites;
+  const uint32_t L = (uint32_t)P.freq_levels.size();
+  std::vector<nghmm_freq_stat> st(S);
+  std::vector<double> curve((size_t)S * L);
+  check(nghmm_chain_freq_info(C.hs.data(), C.n(), L, L ? P.freq_levels.data() : nullptr, st.data(),
+                              L ? curve.data() : nullptr, nullptr),
+        "freq_info");
+  const std::string name = P.prefix + ".freq.info";
+  FILE* fh = fopen(name.c_str(), "w");
+  if (!fh) fatal(__FUNCTION__, "cannot open frequency information output file!");
+  setvbuf(fh, nullptr, _IOFBF, 1 << 22);
+  fputs("chr\tpos\tfreq\tse\tll\tscore\tinfo", fh);
+  for (uint32_t k = 0; k < L; k++) fprintf(fh, "\tdll_%g", P.freq_levels[k]);
+  fputc('\n', fh);
+  size_t c = 0;
+  for (uint64_t s = 0; s < S; s++) {
+    while (c + 1 < P.chrom_first.size() && P.chrom_first[c + 1] <= s) c++;
+    const nghmm_freq_stat& t = st[s];
+    const bool ok = t.info > 0 && t.freq > 0 && t.freq < 1;
+    fprintf(fh, "%s\t%llu", P.chrom_name[c].c_str(), (unsigned long long)P.site_pos[s]);
+    put_g10(fh, t.freq);
+    put_g10(fh, ok ? 1.0 / sqrt(t.info) : NAN);
+    put_g10(fh, t.ll);
+    put_g10(fh, t.score);
+    put_g10(fh, t.info);
+    for (uint32_t k = 0; k < L; k++) put_g10(fh, curve[(size_t)s * L + k]);
+    fputc('\n', fh);
+  }
+  if (fclose(fh) != 0) fatal(__FUNCTION__, "cannot write the frequency information output file!");
+}
+
 void sync_outputs(Params& P, Cohort& C, bool with_viterbi) {
   P.path.resize((size_t)P.n_ind * P.n_sites, 0);
   // indF / alpha are the cohort's on every handle; the frequencies those of its own sites
@@ -1688,6 +1743,7 @@ void parse_cmd_args(Params& P, int argc, char** argv) {  // parse_args.cpp:41-22
       {"ibd_sharing", no_argument, nullptr, 1020},    {"sharing_thresh", required_argument, nullptr, 1021},
       {"ibd_support", no_argument, nullptr, 1022},
       {"ibd_bounds", no_argument, nullptr, 1023},     {"bounds_ci", required_argument, nullptr, 1024},
+      {"freq_info", no_argument, nullptr, 1025},      {"freq_levels", required_argument, nullptr, 1026},
       {0, 0, 0, 0}};
   long taus_kat = 0;
   bool parse_kat = false, se_kat = false;
@@ -1738,6 +1794,22 @@ void parse_cmd_args(Params& P, int argc, char** argv) {  // parse_args.cpp:41-22
       case 1022: P.ibd_support = true; break;
       case 1023: P.ibd_bounds = true; break;
       case 1024: P.bounds_ci = atof(optarg); break;
+      case 1025: P.freq_info = true; break;
+      case 1026: {   // a,b,...: every field a number in [0, 1]
+        P.freq_levels.clear();
+        P.freq_levels_given = true;
+        for (const char* q = optarg;;) {
+          char* e = nullptr;
+          const double v = strtod(q, &e);
+          if (e == q || !(v >= 0.0 && v <= 1.0) || (*e != ',' && *e != 0))
+            fatal(__FUNCTION__, "invalid --freq_levels (frequencies in [0, 1], separated by commas)!");
+          P.freq_levels.push_back(v);
+          if (*e == 0) break;
+          q = e + 1;
+        }
+        if (P.freq_levels.size() > 8) fatal(__FUNCTION__, "invalid --freq_levels (at most 8 levels)!");
+        break;
+      }
       case 1000:
         if (!strcmp(optarg, "exact")) P.mode = NGHMM_MODE_EXACT;
         else if (!strcmp(optarg, "fast")) P.mode = NGHMM_MODE_FAST;
@@ -1847,6 +1919,9 @@ void parse_cmd_args(Params& P, int argc, char** argv) {  // parse_args.cpp:41-22
   if (P.ibd_bounds && !(P.bounds_ci > 0 && P.bounds_ci < 1))
     fatal(__FUNCTION__, "--bounds_ci must be inside (0, 1)!");
   if (!P.ibd_bounds && P.bounds_ci != 0.95) warn(__FUNCTION__, "--bounds_ci is only used by --ibd_bounds");
+  if (P.freq_info && !nghmm_chain_freq_info)
+    fatal(__FUNCTION__, "--freq_info: the library has no nghmm_chain_freq_info!");
+  if (!P.freq_info && P.freq_levels_given) warn(__FUNCTION__, "--freq_levels is only used by --freq_info");
   if (P.min_iters < 1 || P.max_iters < 1 || P.min_iters >= P.max_iters)
     fatal(__FUNCTION__, "invalid number of iterations!");
   if (P.n_threads < 1) fatal(__FUNCTION__, "invalid number of threads!");
@@ -1979,6 +2054,7 @@ void finish_run(Params& P, Cohort& C) {
   if (P.ibd_sharing) write_ibd_sharing(P, C);
   if (P.ibd_support) write_ibd_support(P, C);
   if (P.ibd_bounds) write_ibd_bounds(P, C);
+  if (P.freq_info) write_freq_info(P, C);
   if (P.verbose >= 2)  // (not a line of the reference's)
     fprintf(P.out, "> decoded in %.2f s, output files written in %.2f s\n", t1 - t0, omp_get_wtime() - t1);
 }
@@ -2096,6 +2172,7 @@ int main(int argc, char** argv) {
         runs[r].ibd_sharing = P.ibd_sharing && r == best;
         runs[r].ibd_support = P.ibd_support && r == best;
         runs[r].ibd_bounds = P.ibd_bounds && r == best;
+        runs[r].freq_info = P.freq_info && r == best;
         finish_run(runs[r], cs[r]);
       }
       fclose(runs[r].out);
@@ -2115,6 +2192,7 @@ int main(int argc, char** argv) {
       if (P.ibd_sharing) exts.push_back(".ibd.sharing");
       if (P.ibd_support) exts.push_back(".ibd.support");
       if (P.ibd_bounds) exts.push_back(".ibd.bounds");
+      if (P.freq_info) exts.push_back(".freq.info");
       for (unsigned k = 1; P.sample_paths && k <= P.sample_keep; k++) {
         char tag[32];
         snprintf(tag, sizeof tag, ".sample_%02u.ibd", k);

@@ -150,6 +150,8 @@ def load_library():
         "nghmm_chain_tract_support": (i32, [C.POINTER(vp), i32, vp, u64, vp]),
         "nghmm_tract_bounds": (i32, [vp, vp, u64, vp, dp, u32, vp, vp, vp]),
         "nghmm_chain_tract_bounds": (i32, [C.POINTER(vp), i32, vp, u64, vp, dp, u32, vp, vp, vp]),
+        "nghmm_freq_info": (i32, [vp, u32, dp, vp, dp, dp]),
+        "nghmm_chain_freq_info": (i32, [C.POINTER(vp), i32, u32, dp, vp, dp, dp]),
         "nghmm_obs_info": (i32, [vp, dp, dp, vp]),
         "nghmm_chain_obs_info": (i32, [C.POINTER(vp), i32, dp, dp, vp]),
         "nghmm_ibd_summary": (i32, [vp, i32, d, u64, C.POINTER(u64), C.POINTER(u64), vp, vp]),
@@ -197,6 +199,7 @@ EXPORTED_SYMBOLS = [
     "nghmm_sample_paths", "nghmm_chain_sample_paths",
     "nghmm_tract_support", "nghmm_chain_tract_support",
     "nghmm_tract_bounds", "nghmm_chain_tract_bounds",
+    "nghmm_freq_info", "nghmm_chain_freq_info",
     "nghmm_obs_info", "nghmm_chain_obs_info",
     "nghmm_ibd_summary", "nghmm_chain_ibd_summary",
     "nghmm_ibd_sharing", "nghmm_chain_ibd_sharing",
@@ -374,6 +377,34 @@ def _tract_bounds(call, check, tracts, anchors, levels):
     out["reach_left"] = np.exp(out["log_reach_left"])
     out["reach_right"] = np.exp(out["log_reach_right"])
     return out, start, end
+
+
+# nghmm_freq_stat (include/nghmm.h): one record per site of freq_info
+FREQ_STAT_DTYPE = np.dtype([("freq", np.float64), ("ll", np.float64), ("score", np.float64),
+                            ("info", np.float64)])
+
+
+def _freq_info(call, check, n_ind, n_sites, levels, cavity):
+    lv = np.ascontiguousarray(np.asarray(levels, dtype=np.float64))
+    if lv.ndim != 1:
+        raise NgsFHMMError(-10, "freq_info: levels is a sequence of frequencies")
+    m = len(lv)
+    stats = np.zeros(n_sites, dtype=FREQ_STAT_DTYPE)
+    curve = np.zeros((n_sites, m))
+    cav = np.zeros((n_ind, n_sites)) if cavity else None
+    check(call(m, _dp(lv) if m else None, C.c_void_p(stats.ctypes.data), _dp(curve) if m else None,
+               _dp(cav) if cavity else None))
+    return (stats, curve, cav) if cavity else (stats, curve)
+
+
+def freq_std_errors(stats):
+    """Standard errors of the allele frequencies from freq_info's records taken AT the estimates:
+    1 / sqrt(info) where info > 0 and 0 < freq < 1, else NaN.  They are conditional on indF, alpha
+    and the other sites' frequencies, which freq_info holds fixed."""
+    info, f = np.asarray(stats["info"]), np.asarray(stats["freq"])
+    ok = (info > 0) & (f > 0) & (f < 1)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return np.where(ok, 1.0 / np.sqrt(np.where(ok, info, 1.0)), np.nan)
 
 
 # nghmm_path_stats (include/nghmm.h): one record per (draw, individual) of sample_paths
@@ -999,6 +1030,19 @@ class NgsFHMM:
         return _tract_bounds(lambda *a: self.lib.nghmm_tract_bounds(self._h, *a), self._check, tracts,
                              anchors, levels)
 
+    def freq_info(self, levels=(), cavity=False):
+        """Per site the log-likelihood of the whole cohort as a function of that site's allele
+        frequency alone, at the CURRENT indF, alpha and freq (nghmm_freq_info).  Returns (stats,
+        curve), or with cavity=True (stats, curve, cavity): stats, a structured array [S] of
+        FREQ_STAT_DTYPE (freq, the leave-one-site-out log-likelihood ll of the site's data, its
+        derivative score and minus its second derivative info at freq); curve [S][len(levels)],
+        the log-likelihood at every level minus the one at freq (levels: at most 8, in [0, 1]; at
+        0 or 1, -2 curve is a likelihood-ratio statistic against a monomorphic site); cavity
+        [I][S], P(IBD at the site | all data of the individual except the site's).
+        freq_std_errors turns the records into standard errors."""
+        return _freq_info(lambda *a: self.lib.nghmm_freq_info(self._h, *a), self._check, self.n_ind,
+                          self.n_sites, levels, cavity)
+
     def obs_info(self, indF=None, alpha=None):
         """Per individual the log-likelihood, its gradient and its Hessian in (indF, alpha) under
         the current emissions, from exact derivatives (nghmm_obs_info): a structured array [I] of
@@ -1168,6 +1212,12 @@ class Chain:
         return _tract_bounds(
             lambda *a: self.lib.nghmm_chain_tract_bounds(self._arr, len(self.handles), *a),
             self.handles[0]._check, tracts, anchors, levels)
+
+    def freq_info(self, levels=(), cavity=False):
+        """NgsFHMM.freq_info over the chain (nghmm_chain_freq_info): global site order."""
+        self._members_open()
+        return _freq_info(lambda *a: self.lib.nghmm_chain_freq_info(self._arr, len(self.handles), *a),
+                          self.handles[0]._check, self.n_ind, self.n_sites, levels, cavity)
 
     def obs_info(self, indF=None, alpha=None):
         """NgsFHMM.obs_info over the chain (nghmm_chain_obs_info)."""
