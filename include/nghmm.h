@@ -572,6 +572,102 @@ int nghmm_freq_info(nghmm_t* h, uint32_t n_levels, const double* levels, nghmm_f
 int nghmm_chain_freq_info(nghmm_t** hs, int n_handles, uint32_t n_levels, const double* levels,
                           nghmm_freq_stat* stats, double* curve, double* cavity);
 
+/* ---- genotype posteriors under the HMM: calls, heterozygosity, the EM update of a frequency ----
+ * The posterior of a cell's genotype given ALL data of the individual, with the IBD state of the
+ * site summed out exactly.  nghmm_geno_posteriors (the reference's print_iter) uses the hard
+ * Viterbi state as the site's inbreeding coefficient: one wrongly decoded site flips the prior of
+ * the heterozygote between 2f(1 - f) and 0, and no heterozygote can be called where the path says
+ * IBD.  Putting the marginal posterior there (EM.cpp:371, commented out) counts the site's own
+ * data twice.  (The reference has no such function.)
+ *
+ * Definition.  For cell (i, s), at the handle's CURRENT indF, alpha and freq:
+ *     (w0, w1) = (1 - c, c), the two cavity weights exactly as nghmm_freq_info defines and forms
+ *                them (each from its own product, never as 1 - x);
+ *     p_g = exp(gl_g), f = freq[s];
+ *     h0 = ((1 - f)^2, 2 f (1 - f), f^2),  h1 = (1 - f, 0, f)     (calc_HWE with F = 0 and F = 1)
+ *     J[z][g] = w_z h_z[g] p_g                      six products; J[1][1] = 0
+ *     B       = sum J = (1 - c) e0 + c e1           nghmm_freq_info's bracket
+ *     P_g     = (J[0][g] + J[1][g]) / B             the smoothed genotype posterior
+ *     pi      = (J[1][0] + J[1][2]) / B             the smoothed IBD posterior (unsnapped)
+ *     non     = (J[0][0] + J[0][1] + J[0][2]) / B   1 - pi, from its own sum
+ * J / B is the joint posterior of (z_is, g_is) given all data of individual i: it equals the
+ * enumeration over all paths.  A called genotype (one p_g = 1, the others 0) has B equal to its
+ * one numerator: the posterior is one-hot exactly.  A missing cell gets the cavity-weighted prior.
+ *
+ *   post [S][I][3]   P_0, P_1, P_2 (site-major: the cell order of nghmm_geno_posteriors)
+ *   call [S][I]      the g with the largest P_g, ties to the lowest g; 3 where B = 0 or the
+ *                    posterior is NaN
+ *   sites [S]        sums over the individuals:
+ *                    n0, n1, n2   P_g: the expected genotype counts
+ *                    het_prior    w0 2 f (1 - f): the heterozygotes expected before the site's own
+ *                                 data are seen (n1 / het_prior far above 1 marks paralogous or
+ *                                 mis-mapped sites)
+ *                    ibd          pi
+ *                    alt_ibd      J[1][2] / B: the IBD individuals that carry the alternative allele
+ *   regions [I][n_regions]   sums over the region's sites:
+ *                    het          P_1
+ *                    het_prior    w0 2 f (1 - f)
+ *                    non_ibd      non
+ *                    dosage       P_1 + 2 P_2
+ *                    het / non_ibd is the heterozygosity outside IBD; het / het_prior the excess
+ *                    against the model.
+ * Two identities.  (a) The EXACT EM update of f_s under the model is alternative allele copies over
+ * allele copies, an IBD individual carrying one copy:
+ *     em_freq = (n1 + 2 n2 - alt_ibd) / (2 I - ibd),
+ * and by Fisher's identity  score f (1 - f) = (n1 + 2 n2 - alt_ibd) - f (2 I - ibd)  with
+ * nghmm_freq_info's score: em_freq - freq is that score in frequency units, 0 exactly where the
+ * likelihood is stationary in f_s (est_maf's mean-field step need not end there).  (b) Called
+ * genotypes give one-hot posteriors, see above.
+ * Everything is CONDITIONAL on indF, alpha and the frequencies, as nghmm_freq_info's results are.
+ *
+ * Dead cells.  B = 0 only where a called genotype meets a frequency of 0 or 1 that excludes it:
+ * the cell has NaN in post and 3 in call, and the NaN stays in the sums it enters (all of a site's
+ * and a region's but het_prior).  Nothing else is ever NaN.
+ *
+ * Evaluation.  The walks of nghmm_freq_info, then one pass over the weights
+ * and the likelihoods.  No float atomics.  A site's sums run over the individuals in blocks of 64;
+ * within a block (filled up with zeros) a butterfly -- x_i += x_{i ^ 32}, then ^ 16, 8, 4, 2, 1 --;
+ * the blocks are added in order, the first one's value first (nghmm_freq_info's rule).  A region's
+ * sums follow nghmm_ibd_summary's rule for post_sum: the region is cut at the multiples of 2048 of
+ * the handle's own sites, every piece is summed from 0 in site order, and the pieces are added in
+ * site order, the first one's value first.  The same bits on every call, and every output's bits
+ * do not depend on which other outputs are asked for. */
+typedef struct nghmm_geno_site_stat {  /* 48 bytes; one per site */
+  double n0, n1, n2, het_prior, ibd, alt_ibd;
+} nghmm_geno_site_stat;
+typedef struct nghmm_geno_region_stat {  /* 32 bytes; one per individual and region */
+  double het, het_prior, non_ibd, dosage;
+} nghmm_geno_region_stat;
+#ifdef __cplusplus
+static_assert(sizeof(nghmm_geno_site_stat) == 48, "nghmm_geno_site_stat is 48 bytes");
+static_assert(sizeof(nghmm_geno_region_stat) == 32, "nghmm_geno_region_stat is 32 bytes");
+#endif
+/* region_begin, region_end [n_regions], regions [I][n_regions], sites [S], post [S][I][3], call
+ * [S][I] (all host).  Regions are nghmm_ibd_summary's: half-open [begin, end), sorted, disjoint,
+ * not empty, inside the data; regions, region_begin and region_end are NULL iff n_regions == 0.
+ * Every output may be NULL; at least one is not.  NGHMM_ERR_ARG, with a message, for a handle
+ * without data, all outputs NULL, the NULL mismatch and bad regions.
+ * Self-contained and read-only exactly like nghmm_freq_info: it forms its own emissions from the
+ * likelihoods and the current frequencies, and leaves parameters, emissions, posteriors, Viterbi
+ * path, checkpoints and a planned M-step untouched; an EM iteration after the call gives the bits
+ * it would have given without it.  A NaN in the walks raises the invalid-likelihood error, as
+ * there.  Device scratch, kept by the handle in an owner of its own: 16 bytes per cell for the
+ * weights, 24 more when post is asked for, 1 more for call, and the records (NGHMM_ERR_NOMEM when
+ * it cannot be had). */
+int nghmm_geno_smooth(nghmm_t* h, uint64_t n_regions, const uint64_t* region_begin,
+                      const uint64_t* region_end, nghmm_geno_region_stat* regions,
+                      nghmm_geno_site_stat* sites, double* post, uint8_t* call);
+/* The same over a chain of site shards (nghmm_chain_setup, else NGHMM_ERR_ARG): global site
+ * indices.  post, call and sites are the concatenation of the shards' and THE SINGLE HANDLE'S
+ * BYTES: they depend only on the cell and on the cavity, which has that property
+ * (nghmm_chain_freq_info).  A region that crosses a cut is one region, its shards' parts added on
+ * the host in rank order: within rounding of the single handle's sums, not their bytes, as for
+ * nghmm_chain_ibd_summary.  (Chains of more than one handle are fast mode only.) */
+int nghmm_chain_geno_smooth(nghmm_t** hs, int n_handles, uint64_t n_regions,
+                            const uint64_t* region_begin, const uint64_t* region_end,
+                            nghmm_geno_region_stat* regions, nghmm_geno_site_stat* sites,
+                            double* post, uint8_t* call);
+
 /* ---- observed information of indF and alpha ----
  * Per individual the log-likelihood, its gradient and its 2x2 Hessian in (F, alpha) at one point,
  * from EXACT derivatives carried through one forward pass (no finite differences): what standard

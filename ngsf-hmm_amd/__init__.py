@@ -21,7 +21,8 @@ from .hmm import (NgsFHMM, NgsFHMMError, Group, Chain, MODE_EXACT, MODE_FAST, GE
                   SUMMARY_SEGMENT_SITES, REGION_STAT_DTYPE, SITE_STAT_DTYPE, chromosome_regions,
                   window_regions, SHARING_VITERBI, SHARING_POSTERIOR, SHARING_SPLIT_SITES,
                   sharing_splits, sharing_jaccard, TractScore, TRACT_SCORE_DTYPE, TractBound,
-                  TRACT_BOUND_DTYPE, NO_ANCHOR, FREQ_STAT_DTYPE, freq_std_errors)
+                  TRACT_BOUND_DTYPE, NO_ANCHOR, FREQ_STAT_DTYPE, freq_std_errors,
+                  GENO_SITE_STAT_DTYPE, GENO_REGION_STAT_DTYPE, geno_em_freq, het_outside_ibd)
 from . import simulate
 
 __all__ = ["NgsFHMM", "NgsFHMMError", "Group", "Chain", "MODE_EXACT", "MODE_FAST", "GENO_PACKED", "LD_INTENDED", "EPROB_LD", "library_path",
@@ -31,4 +32,5 @@ __all__ = ["NgsFHMM", "NgsFHMMError", "Group", "Chain", "MODE_EXACT", "MODE_FAST
            "chromosome_regions", "window_regions", "SHARING_VITERBI", "SHARING_POSTERIOR",
            "SHARING_SPLIT_SITES", "sharing_splits", "sharing_jaccard", "TractScore",
            "TRACT_SCORE_DTYPE", "TractBound", "TRACT_BOUND_DTYPE", "NO_ANCHOR",
-           "FREQ_STAT_DTYPE", "freq_std_errors"]
+           "FREQ_STAT_DTYPE", "freq_std_errors", "GENO_SITE_STAT_DTYPE", "GENO_REGION_STAT_DTYPE",
+           "geno_em_freq", "het_outside_ibd"]

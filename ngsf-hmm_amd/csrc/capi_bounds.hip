@@ -27,8 +27,6 @@ namespace {
 
 constexpr double kNegInf = -std::numeric_limits<double>::infinity();
 
-uint64_t align256(uint64_t n) { return (n + 255) & ~255ull; }
-
 // a range of a pass in global sites
 struct Range {
   uint32_t ind;

@@ -6,7 +6,8 @@
 // from the vector the shard before ended with, then the backward walks from the last to the first,
 // I x 2 doubles per boundary; every vector is a plain site-by-site recursion, so the shards
 // continue the single handle's arithmetic bit for bit and the outputs are the concatenation of the
-// shards'.
+// shards'.  The walks and their vectors are cavity_walks (capi_cavity.hip), which
+// capi_genosmooth.hip drives too; what this file makes of the weights is the site pass.
 // (implementation of include/nghmm.h; capi_internal.hpp has the handle and the shared helpers.)
 #include "capi_internal.hpp"
 #include "kernels_freqinfo.hpp"
@@ -15,42 +16,6 @@ static_assert(sizeof(nghmm_freq_stat) == 32, "nghmm_freq_stat is 32 bytes");
 static_assert(sizeof(FreqStat) == sizeof(nghmm_freq_stat), "the device's record is nghmm_freq_stat");
 
 namespace {
-
-uint64_t align256(uint64_t n) { return (n + 255) & ~255ull; }
-
-// the handle's scratch (h->d_finfo), carved
-struct Carve {
-  double *vin, *vout, *cav, *curve, *cav_out;
-  FreqStat* stats;
-  uint64_t* seg;
-  uint64_t n_seg = 0;
-};
-
-int carve(nghmm_t* h, uint64_t n_seg, uint32_t n_levels, bool want_cavity, Carve& c) {
-  const uint64_t I = h->I, S = h->S;
-  const uint64_t b_vec = align256(I * 2 * sizeof(double));
-  const uint64_t b_cav = align256(S * I * 2 * sizeof(double)), b_seg = align256((n_seg + 1) * sizeof(uint64_t));
-  const uint64_t b_stats = align256(S * sizeof(FreqStat)), b_curve = align256(S * n_levels * sizeof(double));
-  const uint64_t b_out = want_cavity ? align256(S * I * sizeof(double)) : 0;
-  int rc;
-  if ((rc = h->d_finfo.reserve(2 * b_vec + b_seg + b_cav + b_stats + b_curve + b_out))) return rc;
-  uint8_t* p = h->d_finfo.p;
-  c.vin = reinterpret_cast<double*>(p);
-  p += b_vec;
-  c.vout = reinterpret_cast<double*>(p);
-  p += b_vec;
-  c.seg = reinterpret_cast<uint64_t*>(p);
-  p += b_seg;
-  c.n_seg = n_seg;
-  c.cav = reinterpret_cast<double*>(p);
-  p += b_cav;
-  c.stats = reinterpret_cast<FreqStat*>(p);
-  p += b_stats;
-  c.curve = reinterpret_cast<double*>(p);
-  p += b_curve;
-  c.cav_out = reinterpret_cast<double*>(p);
-  return NGHMM_OK;
-}
 
 int freqinfo_impl(nghmm_t** hs, int n, uint32_t n_levels, const double* levels, nghmm_freq_stat* stats,
                   double* curve, double* cavity, const char* who) {
@@ -93,79 +58,33 @@ int freqinfo_impl(nghmm_t** hs, int n, uint32_t n_levels, const double* levels, 
     base[r] = S_tot;
     S_tot += hs[r]->S;
   }
-  int rc;
-  std::vector<Carve> cv(n);
-  std::vector<double> vec((size_t)I * 2);
-  // scratch and segments; the forward walks, first shard to last
-  std::vector<double> pos;
-  std::vector<uint64_t> seg;
-  for (int r = 0; r < n; ++r) {
-    nghmm_t* h = hs[r];
-    const uint64_t S = h->S;
-    if ((rc = use_device(h))) return rc;
-    if (fast) {
-      pos.resize(S);
-      HIP_TRY(hipMemcpyAsync(pos.data(), h->d_pos, S * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-      HIP_TRY(sync_stream(h));
-      seg.clear();
-      for (uint64_t s = 0; s < S; ++s)
-        if (s == 0 || freqinfo_chrom_start(pos[s])) seg.push_back(s);
-      seg.push_back(S);
-    }
-    if ((rc = carve(h, fast ? seg.size() - 1 : 0, n_levels, cavity != nullptr, cv[r]))) return rc;
-    if ((rc = clear_flags(h))) return rc;
-    if (!fast) continue;
-    const Carve& c = cv[r];
-    HIP_TRY(hipMemcpyAsync(c.seg, seg.data(), seg.size() * sizeof(uint64_t), hipMemcpyHostToDevice, h->stream));
-    if (r > 0) HIP_TRY(hipMemcpyAsync(c.vin, vec.data(), I * 2 * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    if (!freqinfo_fast_walks(h->stream, fast_gl_lin(h->fast), h->d_freq, h->d_pos, c.seg, c.n_seg, S, I,
-                             h->d_indF, h->d_alpha, r ? c.vin : nullptr, r + 1 < n ? c.vout : nullptr,
-                             nullptr, nullptr, c.cav, h->d_flags, false)) {
-      set_error("%s: a kernel launch failed", who);
-      return NGHMM_ERR_HIP;
-    }
-    if (r + 1 < n)
-      HIP_TRY(hipMemcpyAsync(vec.data(), c.vout, I * 2 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(sync_stream(h));   // (seg and vec are the host's to reuse)
-  }
-  // the backward walks, last shard to first; behind each the shard's site pass
+  // the caller's bytes of a shard: the site records | the curve | c of every cell [I][S]
+  auto b_stats = [&](int r) { return align256(hs[r]->S * sizeof(FreqStat)); };
+  auto b_curve = [&](int r) { return align256(hs[r]->S * n_levels * sizeof(double)); };
+  auto extra_bytes = [&](int r) {
+    return b_stats(r) + b_curve(r) + (cavity ? align256(hs[r]->S * I * sizeof(double)) : 0);
+  };
   std::vector<double> rows;
-  for (int r = n - 1; r >= 0; --r) {
+  // behind a shard's backward walk: its site pass and its copies
+  auto shard_done = [&](int r, const double* d_cav, uint8_t* extra) -> int {
     nghmm_t* h = hs[r];
-    const Carve& c = cv[r];
     const uint64_t S = h->S;
-    const bool last = r == n - 1;
-    if ((rc = use_device(h))) return rc;
-    if (fast) {
-      if (!last) HIP_TRY(hipMemcpyAsync(c.vin, vec.data(), I * 2 * sizeof(double), hipMemcpyHostToDevice, h->stream));
-      if (!freqinfo_fast_walks(h->stream, fast_gl_lin(h->fast), h->d_freq, h->d_pos, c.seg, c.n_seg, S, I,
-                               h->d_indF, h->d_alpha, nullptr, nullptr, last ? nullptr : c.vin,
-                               r > 0 ? c.vout : nullptr, c.cav, h->d_flags, true) ||
-          !freqinfo_sites(h->stream, c.cav, fast_gl_lin(h->fast), false, h->d_freq, S, I, lv, c.stats,
-                          c.curve)) {
-        set_error("%s: a kernel launch failed", who);
-        return NGHMM_ERR_HIP;
-      }
-      if (r > 0) HIP_TRY(hipMemcpyAsync(vec.data(), c.vout, I * 2 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    } else {
-      launch_freqinfo_exact(h->stream, own_gl(h), h->d_freq, h->d_pos, h->d_fw, S, I, h->d_indF, h->d_alpha,
-                            c.cav, h->d_flags);
-      HIP_TRY(hipGetLastError());
-      if (!freqinfo_sites(h->stream, c.cav, own_gl(h), true, h->d_freq, S, I, lv, c.stats, c.curve)) {
-        set_error("%s: a kernel launch failed", who);
-        return NGHMM_ERR_HIP;
-      }
-    }
-    if (cavity && !freqinfo_cavity_out(h->stream, c.cav, S, I, c.cav_out)) {
+    int rc;
+    FreqStat* d_stats = reinterpret_cast<FreqStat*>(extra);
+    double* d_curve = reinterpret_cast<double*>(extra + b_stats(r));
+    double* d_cav_out = reinterpret_cast<double*>(extra + b_stats(r) + b_curve(r));
+    if (!freqinfo_sites(h->stream, d_cav, fast ? fast_gl_lin(h->fast) : own_gl(h), !fast, h->d_freq, S, I, lv,
+                        d_stats, d_curve) ||
+        (cavity && !freqinfo_cavity_out(h->stream, d_cav, S, I, d_cav_out))) {
       set_error("%s: a kernel launch failed", who);
       return NGHMM_ERR_HIP;
     }
     HIP_TRY(hipGetLastError());
     if ((rc = check_flags(h))) return rc;   // (waits for the stream)
     if (stats)
-      HIP_TRY(hipMemcpyAsync(stats + base[r], c.stats, S * sizeof(FreqStat), hipMemcpyDeviceToHost, h->stream));
+      HIP_TRY(hipMemcpyAsync(stats + base[r], d_stats, S * sizeof(FreqStat), hipMemcpyDeviceToHost, h->stream));
     if (curve)
-      HIP_TRY(hipMemcpyAsync(curve + base[r] * n_levels, c.curve, S * n_levels * sizeof(double),
+      HIP_TRY(hipMemcpyAsync(curve + base[r] * n_levels, d_curve, S * n_levels * sizeof(double),
                              hipMemcpyDeviceToHost, h->stream));
     if (cavity) {
       double* dst = cavity;
@@ -173,14 +92,15 @@ int freqinfo_impl(nghmm_t** hs, int n, uint32_t n_levels, const double* levels, 
         rows.resize((size_t)I * S);
         dst = rows.data();
       }
-      HIP_TRY(hipMemcpyAsync(dst, c.cav_out, I * S * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+      HIP_TRY(hipMemcpyAsync(dst, d_cav_out, I * S * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     }
     HIP_TRY(sync_stream(h));
     if (cavity && n > 1)
       for (uint64_t i = 0; i < I; ++i)
         std::memcpy(cavity + i * S_tot + base[r], rows.data() + i * S, S * sizeof(double));
-  }
-  return NGHMM_OK;
+    return NGHMM_OK;
+  };
+  return cavity_walks(hs, n, &nghmm_handle::d_finfo, extra_bytes, shard_done, who);
 }
 
 }  // namespace

@@ -1,6 +1,6 @@
 // capi_internal.hpp -- what the translation units of the C ABI share: the handle, error plumbing,
 // and the helpers every entry point uses.  nghmm_capi.hip (handle life cycle, single-handle EM),
-// capi_load.hip (loaders), capi_output.hip (read-back and output formatting), capi_tracts.hip, capi_sample.hip, capi_info.hip, capi_summary.hip, capi_sharing.hip, capi_support.hip, capi_bounds.hip, capi_freqinfo.hip and
+// capi_load.hip (loaders), capi_output.hip (read-back and output formatting), capi_tracts.hip, capi_sample.hip, capi_info.hip, capi_summary.hip, capi_sharing.hip, capi_support.hip, capi_bounds.hip, capi_cavity.hip, capi_freqinfo.hip, capi_genosmooth.hip and
 // capi_multi.hip (individual shards, site shards, groups and chains of handles) implement include/nghmm.h.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -118,6 +118,9 @@ struct nghmm_handle {
   // per-site likelihood in the frequency (capi_freqinfo.hip): the boundary vectors, the cavity
   // weights of every cell, the site records and the curve
   DevScratch<uint8_t> d_finfo;
+  // genotype posteriors under the HMM (capi_genosmooth.hip): the boundary vectors, the cavity
+  // weights of every cell, the posteriors, the calls, the records and the pieces
+  DevScratch<uint8_t> d_gsm;
   DevBuf<double> d_freq_new, d_hap;  // --freq_est 2 as intended: [S], [S][4]
 
   // multi-GPU shard
@@ -194,6 +197,9 @@ struct nghmm_handle {
 
 namespace capi {
 
+// a carved scratch keeps every part 256-byte aligned
+inline uint64_t align256(uint64_t n) { return (n + 255) & ~255ull; }
+
 hipError_t sync_stream(nghmm_t* h);
 int use_device(nghmm_t* h);
 void tic(nghmm_t* h);
@@ -245,6 +251,12 @@ struct SummaryRegion {
   uint64_t begin, end;
   bool first;
 };
+// The regions of one handle (sorted, disjoint, inside [0, S)) cut into pieces at the segment
+// edges (the multiples of kSummarySeg), in site order: pieces, seg_piece [summary_segments(S) + 1]
+// (the first piece of every segment) and piece_first [regs.size() + 1] (the first piece of every
+// region), as launch_summary_pass and the finish kernels take them
+void summary_cut_pieces(const std::vector<SummaryRegion>& regs, uint64_t S, std::vector<SummaryPiece>& pieces,
+                        std::vector<uint32_t>& seg_piece, std::vector<uint32_t>& piece_first);
 // the summary of one handle to the host: regions [I][regs.size()] (NULL iff there are none),
 // sites [S] (may be NULL); prev_state [I] (host, may be NULL = all 0)
 int summary_to_host(nghmm_t* h, int what, double thr, const std::vector<SummaryRegion>& regs,
@@ -259,5 +271,18 @@ int sharing_check_range(uint64_t S, uint64_t site_begin, uint64_t site_end, cons
 // output is not computed
 int sharing_to_host(nghmm_t* h, double thr, uint64_t begin, uint64_t end, uint64_t* vit_both,
                     uint64_t* post_both, double* post_prod);
+// The cavity weights (1 - c, c) of every cell of a handle or a chain of site shards, at the
+// CURRENT indF, alpha and freq (capi_cavity.hip; kernels_freqinfo.hpp has the walks): the
+// segments, the forward walks from the first shard to the last, the backward walks from the last
+// to the first, the boundary vectors through the host.  The scratch of shard r lives in
+// hs[r]->*owner: the walks' own, then extra_bytes(r) bytes for the caller (256-byte aligned).
+// Behind shard r's backward walk, on its stream and with its device current, shard_done(r, d_cav
+// [S][I][2], the caller's bytes) queues what the caller makes of the weights, checks the handle's
+// flags (check_flags: a NaN weight raises FLAG_INVALID_LKL) and copies its results out.
+// The callers check their arguments first: every handle holds data, a chain of more than one is
+// fast mode.
+int cavity_walks(nghmm_t** hs, int n, DevScratch<uint8_t> nghmm_handle::*owner,
+                 const std::function<uint64_t(int)>& extra_bytes,
+                 const std::function<int(int, const double*, uint8_t*)>& shard_done, const char* who);
 
 }  // namespace capi

@@ -77,6 +77,31 @@ size_t round_up(size_t n, size_t a) { return (n + a - 1) / a * a; }
 
 }  // namespace
 
+void summary_cut_pieces(const std::vector<SummaryRegion>& regs, uint64_t S, std::vector<SummaryPiece>& pieces,
+                        std::vector<uint32_t>& seg_piece, std::vector<uint32_t>& piece_first) {
+  const uint64_t nseg = summary_segments(S), R = regs.size();
+  pieces.clear();
+  seg_piece.assign(nseg + 1, 0);
+  piece_first.assign(R + 1, 0);
+  for (uint64_t r = 0; r < R; ++r) {
+    piece_first[r] = (uint32_t)pieces.size();
+    for (uint64_t lo = regs[r].begin; lo < regs[r].end;) {
+      const uint64_t edge = (lo / kSummarySeg + 1) * kSummarySeg;
+      const uint64_t hi = edge < regs[r].end ? edge : regs[r].end;
+      SummaryPiece p;
+      p.lo = lo;
+      p.hi = hi;
+      p.region = (uint32_t)r;
+      p.first = lo == regs[r].begin && regs[r].first ? 1u : 0u;
+      ++seg_piece[lo / kSummarySeg + 1];
+      pieces.push_back(p);
+      lo = hi;
+    }
+  }
+  piece_first[R] = (uint32_t)pieces.size();
+  for (uint64_t g = 0; g < nseg; ++g) seg_piece[g + 1] += seg_piece[g];
+}
+
 int summary_last_state(nghmm_t* h, uint8_t* out) {
   int rc;
   if ((rc = use_device(h))) return rc;
@@ -99,24 +124,8 @@ int summary_to_host(nghmm_t* h, int what, double thr, const std::vector<SummaryR
   const uint64_t S = h->S, I = h->I, nseg = summary_segments(S), nib = (I + 63) / 64, R = regs.size();
   // the pieces: every region cut at the segment edges, in site order
   std::vector<SummaryPiece> pieces;
-  std::vector<uint32_t> seg_piece(nseg + 1, 0), piece_first(R + 1, 0);
-  for (uint64_t r = 0; r < R; ++r) {
-    piece_first[r] = (uint32_t)pieces.size();
-    for (uint64_t lo = regs[r].begin; lo < regs[r].end;) {
-      const uint64_t edge = (lo / kSummarySeg + 1) * kSummarySeg;
-      const uint64_t hi = edge < regs[r].end ? edge : regs[r].end;
-      SummaryPiece p;
-      p.lo = lo;
-      p.hi = hi;
-      p.region = (uint32_t)r;
-      p.first = lo == regs[r].begin && regs[r].first ? 1u : 0u;
-      ++seg_piece[lo / kSummarySeg + 1];
-      pieces.push_back(p);
-      lo = hi;
-    }
-  }
-  piece_first[R] = (uint32_t)pieces.size();
-  for (uint64_t g = 0; g < nseg; ++g) seg_piece[g + 1] += seg_piece[g];
+  std::vector<uint32_t> seg_piece, piece_first;
+  summary_cut_pieces(regs, S, pieces, seg_piece, piece_first);
   const uint64_t np = pieces.size();
   // d_summ: piece records [np][I] | region records [I][R] | site partials [nib][S] (nib > 1) |
   // site records [S] | pieces [np] | segment starts [nseg + 1] | region starts [R + 1] | state [I]

@@ -15,8 +15,6 @@ static_assert(sizeof(SupportScore) == sizeof(nghmm_tract_score), "the device's r
 
 namespace {
 
-uint64_t align256(uint64_t n) { return (n + 255) & ~255ull; }
-
 struct Shard {
   uint64_t base = 0;                  // global index of its first site
   std::vector<SupportRange> rec;      // its parts of the ranges, handle-local

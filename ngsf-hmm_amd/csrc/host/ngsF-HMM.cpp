@@ -26,7 +26,12 @@
 // median of its start and of its end, and the probability that it is one run with either
 // neighbour), --freq_info [--freq_levels a,b,...] (PREFIX.freq.info: per site the log-likelihood of
 // the cohort in that site's allele frequency at the final parameters -- its value, score,
-// information and the standard error made of it, and its change at every level; default level 0).
+// information and the standard error made of it, and its change at every level; default level 0),
+// --geno_smooth (PREFIX.geno.smooth: the genotype posteriors given all data of the individual, the
+// IBD state summed out exactly, raw doubles in the layout of PREFIX.geno), --geno_summary
+// [--geno_window N] (PREFIX.geno.regions and PREFIX.geno.sites: heterozygosity, also outside IBD,
+// and dosage per individual and chromosome or window of N sites; expected genotype counts and the
+// exact EM update of the frequency per site).
 // --n_threads (the reference's pool size) sets the host threads used for input normalisation and output
 // formatting; results do not depend on it.
 #include <fcntl.h>
@@ -74,6 +79,8 @@
 #pragma weak nghmm_chain_tract_bounds
 // ... and without the frequency-information entry: --freq_info then stops with a message
 #pragma weak nghmm_chain_freq_info
+// ... and without the smoothed-genotype entry: --geno_smooth and --geno_summary then stop with a message
+#pragma weak nghmm_chain_geno_smooth
 
 namespace {
 
@@ -148,6 +155,12 @@ struct Params {  // ngsF-HMM.hpp:13-52
   bool freq_info = false;
   std::vector<double> freq_levels = {0.0};
   bool freq_levels_given = false;
+  // --geno_smooth: PREFIX.geno.smooth after every other output -- the genotype posteriors under the
+  // HMM at the final parameters (nghmm_chain_geno_smooth), raw doubles [S][I][3] like PREFIX.geno;
+  // --geno_summary: PREFIX.geno.regions and PREFIX.geno.sites from the same call; regions are the
+  // chromosomes, or with --geno_window N windows of N sites that restart at every chromosome start
+  bool geno_smooth = false, geno_summary = false;
+  uint64_t geno_window = 0;
   std::vector<uint64_t> site_pos;           // [S] the .pos file's integer positions
   std::vector<uint64_t> chrom_first;        // first site of every run of one chromosome name
   std::vector<std::string> chrom_name;      // ... and that name
@@ -1702,6 +1715,90 @@ void write_freq_info(const Params& P, Cohort& C) {
   if (fclose(fh) != 0) fatal(__FUNCTION__, "cannot write the frequency information output file!");
 }
 
+// PREFIX.geno.smooth: raw doubles [S][I][3], the smoothed genotype posteriors in the cell order of
+// PREFIX.geno.
+// PREFIX.geno.regions: a header line, then per individual and region "IND_ID chr first_pos last_pos
+// n_sites het het_prior non_ibd het_out dosage" (tab-separated, ordered by individual, then region;
+// IDs, chromosome names and positions as --ibd_summary writes them): the expected heterozygous
+// sites, the same before the sites' own data are seen, the expected sites outside IBD, het /
+// non_ibd (the heterozygosity outside IBD) and the expected alternative allele copies.
+// PREFIX.geno.sites: a header line, then per site "chr pos n0 n1 n2 het_prior ibd em_freq": the
+// expected genotype counts, the heterozygotes expected before the site's own data are seen, the
+// expected IBD individuals and the exact EM update of the site's frequency.
+// Doubles as %.10g, NaN as NA; everything conditional on the final indF, alpha and frequencies.
+void write_geno_smooth(const Params& P, Cohort& C) {
+  if (!nghmm_chain_geno_smooth)
+    fatal(__FUNCTION__, "--geno_smooth / --geno_summary: the library has no nghmm_chain_geno_smooth!");
+  const uint64_t I = P.n_ind, S = P.n_sites;
+  std::vector<uint64_t> begin, end;
+  std::vector<size_t> chrom;   // the chromosome run of every region
+  if (P.geno_summary)
+    for (size_t c = 0; c < P.chrom_first.size(); c++) {
+      const uint64_t a = P.chrom_first[c], b = c + 1 < P.chrom_first.size() ? P.chrom_first[c + 1] : S;
+      const uint64_t w = P.geno_window ? P.geno_window : b - a;
+      for (uint64_t lo = a; lo < b; lo += w) {
+        begin.push_back(lo);
+        end.push_back(b - lo < w ? b : lo + w);
+        chrom.push_back(c);
+      }
+    }
+  const uint64_t R = begin.size();
+  std::vector<nghmm_geno_region_stat> reg((size_t)I * R);
+  std::vector<nghmm_geno_site_stat> sites(P.geno_summary ? S : 0);
+  std::vector<double> post(P.geno_smooth ? (size_t)S * I * 3 : 0);
+  check(nghmm_chain_geno_smooth(C.hs.data(), C.n(), R, R ? begin.data() : nullptr, R ? end.data() : nullptr,
+                                R ? reg.data() : nullptr, P.geno_summary ? sites.data() : nullptr,
+                                P.geno_smooth ? post.data() : nullptr, nullptr),
+        "geno_smooth");
+  if (P.geno_smooth) {
+    const std::string name = P.prefix + ".geno.smooth";
+    FILE* fh = fopen(name.c_str(), "wb");
+    if (!fh) fatal(__FUNCTION__, "cannot open smoothed genotype output file!");
+    if (fwrite(post.data(), sizeof(double), post.size(), fh) != post.size() || fclose(fh) != 0)
+      fatal(__FUNCTION__, "cannot write the smoothed genotype output file!");
+  }
+  if (!P.geno_summary) return;
+  std::string name = P.prefix + ".geno.regions";
+  FILE* fh = fopen(name.c_str(), "w");
+  if (!fh) fatal(__FUNCTION__, "cannot open genotype region summary output file!");
+  setvbuf(fh, nullptr, _IOFBF, 1 << 22);
+  fputs("ind\tchr\tfirst_pos\tlast_pos\tn_sites\thet\thet_prior\tnon_ibd\thet_out\tdosage\n", fh);
+  for (uint64_t i = 0; i < I; i++) {
+    const std::string id = P.ind_names.empty() ? "ind" + std::to_string(i) : P.ind_names[i];
+    for (uint64_t r = 0; r < R; r++) {
+      const nghmm_geno_region_stat& t = reg[i * R + r];
+      fprintf(fh, "%s\t%s\t%llu\t%llu\t%llu\t", id.c_str(), P.chrom_name[chrom[r]].c_str(),
+              (unsigned long long)P.site_pos[begin[r]], (unsigned long long)P.site_pos[end[r] - 1],
+              (unsigned long long)(end[r] - begin[r]));
+      put_g(fh, t.het, '\t');
+      put_g(fh, t.het_prior, '\t');
+      put_g(fh, t.non_ibd, '\t');
+      put_g(fh, t.non_ibd == 0 ? NAN : t.het / t.non_ibd, '\t');
+      put_g(fh, t.dosage, '\n');
+    }
+  }
+  if (fclose(fh) != 0) fatal(__FUNCTION__, "cannot write the genotype region summary output file!");
+  name = P.prefix + ".geno.sites";
+  fh = fopen(name.c_str(), "w");
+  if (!fh) fatal(__FUNCTION__, "cannot open genotype site summary output file!");
+  setvbuf(fh, nullptr, _IOFBF, 1 << 22);
+  fputs("chr\tpos\tn0\tn1\tn2\thet_prior\tibd\tem_freq\n", fh);
+  size_t c = 0;
+  for (uint64_t s = 0; s < S; s++) {
+    while (c + 1 < P.chrom_first.size() && P.chrom_first[c + 1] <= s) c++;
+    const nghmm_geno_site_stat& t = sites[s];
+    const double den = 2.0 * (double)I - t.ibd;
+    fprintf(fh, "%s\t%llu\t", P.chrom_name[c].c_str(), (unsigned long long)P.site_pos[s]);
+    put_g(fh, t.n0, '\t');
+    put_g(fh, t.n1, '\t');
+    put_g(fh, t.n2, '\t');
+    put_g(fh, t.het_prior, '\t');
+    put_g(fh, t.ibd, '\t');
+    put_g(fh, den == 0 ? NAN : (t.n1 + 2 * t.n2 - t.alt_ibd) / den, '\n');
+  }
+  if (fclose(fh) != 0) fatal(__FUNCTION__, "cannot write the genotype site summary output file!");
+}
+
 void sync_outputs(Params& P, Cohort& C, bool with_viterbi) {
   P.path.resize((size_t)P.n_ind * P.n_sites, 0);
   // indF / alpha are the cohort's on every handle; the frequencies those of its own sites
@@ -1744,6 +1841,8 @@ void parse_cmd_args(Params& P, int argc, char** argv) {  // parse_args.cpp:41-22
       {"ibd_support", no_argument, nullptr, 1022},
       {"ibd_bounds", no_argument, nullptr, 1023},     {"bounds_ci", required_argument, nullptr, 1024},
       {"freq_info", no_argument, nullptr, 1025},      {"freq_levels", required_argument, nullptr, 1026},
+      {"geno_smooth", no_argument, nullptr, 1027},    {"geno_summary", no_argument, nullptr, 1028},
+      {"geno_window", required_argument, nullptr, 1029},
       {0, 0, 0, 0}};
   long taus_kat = 0;
   bool parse_kat = false, se_kat = false;
@@ -1795,6 +1894,12 @@ void parse_cmd_args(Params& P, int argc, char** argv) {  // parse_args.cpp:41-22
       case 1023: P.ibd_bounds = true; break;
       case 1024: P.bounds_ci = atof(optarg); break;
       case 1025: P.freq_info = true; break;
+      case 1027: P.geno_smooth = true; break;
+      case 1028: P.geno_summary = true; break;
+      case 1029:
+        if (atoll(optarg) < 1) fatal(__FUNCTION__, "invalid --geno_window (sites per window)!");
+        P.geno_window = strtoull(optarg, nullptr, 10);
+        break;
       case 1026: {   // a,b,...: every field a number in [0, 1]
         P.freq_levels.clear();
         P.freq_levels_given = true;
@@ -1922,6 +2027,9 @@ void parse_cmd_args(Params& P, int argc, char** argv) {  // parse_args.cpp:41-22
   if (P.freq_info && !nghmm_chain_freq_info)
     fatal(__FUNCTION__, "--freq_info: the library has no nghmm_chain_freq_info!");
   if (!P.freq_info && P.freq_levels_given) warn(__FUNCTION__, "--freq_levels is only used by --freq_info");
+  if ((P.geno_smooth || P.geno_summary) && !nghmm_chain_geno_smooth)
+    fatal(__FUNCTION__, "--geno_smooth / --geno_summary: the library has no nghmm_chain_geno_smooth!");
+  if (!P.geno_summary && P.geno_window) warn(__FUNCTION__, "--geno_window is only used by --geno_summary");
   if (P.min_iters < 1 || P.max_iters < 1 || P.min_iters >= P.max_iters)
     fatal(__FUNCTION__, "invalid number of iterations!");
   if (P.n_threads < 1) fatal(__FUNCTION__, "invalid number of threads!");
@@ -1954,8 +2062,8 @@ void parse_cmd_args(Params& P, int argc, char** argv) {  // parse_args.cpp:41-22
     if (P.ind_names.size() != P.n_ind)
       fatal(__FUNCTION__, "number of lines in --ind_names file is not --n_ind!");
     if (!P.ibd_bed && !P.sample_paths && !P.indF_se && !P.ibd_summary && !P.ibd_sharing && !P.ibd_support &&
-        !P.ibd_bounds)
-      warn(__FUNCTION__, "--ind_names is only used by --ibd_bed, --sample_paths, --indF_se, --ibd_summary, --ibd_sharing, --ibd_support and --ibd_bounds");
+        !P.ibd_bounds && !P.geno_summary)
+      warn(__FUNCTION__, "--ind_names is only used by --ibd_bed, --sample_paths, --indF_se, --ibd_summary, --ibd_sharing, --ibd_support, --ibd_bounds and --geno_summary");
   }
   P.prefix = P.out_prefix;
 }
@@ -2055,6 +2163,7 @@ void finish_run(Params& P, Cohort& C) {
   if (P.ibd_support) write_ibd_support(P, C);
   if (P.ibd_bounds) write_ibd_bounds(P, C);
   if (P.freq_info) write_freq_info(P, C);
+  if (P.geno_smooth || P.geno_summary) write_geno_smooth(P, C);
   if (P.verbose >= 2)  // (not a line of the reference's)
     fprintf(P.out, "> decoded in %.2f s, output files written in %.2f s\n", t1 - t0, omp_get_wtime() - t1);
 }
@@ -2173,6 +2282,8 @@ int main(int argc, char** argv) {
         runs[r].ibd_support = P.ibd_support && r == best;
         runs[r].ibd_bounds = P.ibd_bounds && r == best;
         runs[r].freq_info = P.freq_info && r == best;
+        runs[r].geno_smooth = P.geno_smooth && r == best;
+        runs[r].geno_summary = P.geno_summary && r == best;
         finish_run(runs[r], cs[r]);
       }
       fclose(runs[r].out);
@@ -2193,6 +2304,11 @@ int main(int argc, char** argv) {
       if (P.ibd_support) exts.push_back(".ibd.support");
       if (P.ibd_bounds) exts.push_back(".ibd.bounds");
       if (P.freq_info) exts.push_back(".freq.info");
+      if (P.geno_smooth) exts.push_back(".geno.smooth");
+      if (P.geno_summary) {
+        exts.push_back(".geno.regions");
+        exts.push_back(".geno.sites");
+      }
       for (unsigned k = 1; P.sample_paths && k <= P.sample_keep; k++) {
         char tag[32];
         snprintf(tag, sizeof tag, ".sample_%02u.ibd", k);

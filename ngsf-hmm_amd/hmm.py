@@ -152,6 +152,10 @@ def load_library():
         "nghmm_chain_tract_bounds": (i32, [C.POINTER(vp), i32, vp, u64, vp, dp, u32, vp, vp, vp]),
         "nghmm_freq_info": (i32, [vp, u32, dp, vp, dp, dp]),
         "nghmm_chain_freq_info": (i32, [C.POINTER(vp), i32, u32, dp, vp, dp, dp]),
+        "nghmm_geno_smooth": (i32, [vp, u64, C.POINTER(u64), C.POINTER(u64), vp, vp, dp,
+                                    C.POINTER(C.c_uint8)]),
+        "nghmm_chain_geno_smooth": (i32, [C.POINTER(vp), i32, u64, C.POINTER(u64), C.POINTER(u64), vp,
+                                          vp, dp, C.POINTER(C.c_uint8)]),
         "nghmm_obs_info": (i32, [vp, dp, dp, vp]),
         "nghmm_chain_obs_info": (i32, [C.POINTER(vp), i32, dp, dp, vp]),
         "nghmm_ibd_summary": (i32, [vp, i32, d, u64, C.POINTER(u64), C.POINTER(u64), vp, vp]),
@@ -200,6 +204,7 @@ EXPORTED_SYMBOLS = [
     "nghmm_tract_support", "nghmm_chain_tract_support",
     "nghmm_tract_bounds", "nghmm_chain_tract_bounds",
     "nghmm_freq_info", "nghmm_chain_freq_info",
+    "nghmm_geno_smooth", "nghmm_chain_geno_smooth",
     "nghmm_obs_info", "nghmm_chain_obs_info",
     "nghmm_ibd_summary", "nghmm_chain_ibd_summary",
     "nghmm_ibd_sharing", "nghmm_chain_ibd_sharing",
@@ -405,6 +410,65 @@ def freq_std_errors(stats):
     ok = (info > 0) & (f > 0) & (f < 1)
     with np.errstate(invalid="ignore", divide="ignore"):
         return np.where(ok, 1.0 / np.sqrt(np.where(ok, info, 1.0)), np.nan)
+
+
+# nghmm_geno_site_stat and nghmm_geno_region_stat (include/nghmm.h): one record per site and one
+# per (individual, region) of geno_smooth
+GENO_SITE_STAT_DTYPE = np.dtype([(f, np.float64) for f in ("n0", "n1", "n2", "het_prior", "ibd", "alt_ibd")])
+GENO_REGION_STAT_DTYPE = np.dtype([(f, np.float64) for f in ("het", "het_prior", "non_ibd", "dosage")])
+assert GENO_SITE_STAT_DTYPE.itemsize == 48 and GENO_REGION_STAT_DTYPE.itemsize == 32
+
+
+def _geno_smooth(call_fn, check, n_ind, n_sites, regions, sites, post, call):
+    u64p = C.POINTER(C.c_uint64)
+    if regions is None:
+        reg = np.zeros((0, 2), dtype=np.uint64)
+    else:
+        reg = np.asarray(regions)
+        if reg.size == 0:
+            reg = reg.reshape(0, 2)
+        if reg.ndim != 2 or reg.shape[1] != 2 or not np.issubdtype(reg.dtype, np.integer) or \
+                (reg < 0).any():
+            raise NgsFHMMError(-10, "geno_smooth: regions is an [R][2] array of site indices "
+                                    "(begin, end)")
+        reg = reg.astype(np.uint64)
+    R = len(reg)
+    begin, end = np.ascontiguousarray(reg[:, 0]), np.ascontiguousarray(reg[:, 1])
+    out = {}
+    if R:
+        out["regions"] = np.zeros((n_ind, R), dtype=GENO_REGION_STAT_DTYPE)
+    if sites:
+        out["sites"] = np.zeros(n_sites, dtype=GENO_SITE_STAT_DTYPE)
+    if post:
+        out["post"] = np.zeros((n_sites, n_ind, 3))
+    if call:
+        out["call"] = np.zeros((n_sites, n_ind), dtype=np.uint8)
+    check(call_fn(R, begin.ctypes.data_as(u64p) if R else None, end.ctypes.data_as(u64p) if R else None,
+                  C.c_void_p(out["regions"].ctypes.data) if R else None,
+                  C.c_void_p(out["sites"].ctypes.data) if sites else None,
+                  _dp(out["post"]) if post else None,
+                  out["call"].ctypes.data_as(C.POINTER(C.c_uint8)) if call else None))
+    return out
+
+
+def geno_em_freq(site_stats, n_ind):
+    """The exact EM update of every site's allele frequency under the model, from geno_smooth's
+    site records: (n1 + 2 n2 - alt_ibd) / (2 n_ind - ibd), alternative allele copies over allele
+    copies, an IBD individual carrying one copy; NaN where 2 n_ind - ibd is 0.  em_freq - freq is
+    freq_info's score in frequency units: score f (1 - f) = (em_freq - f) (2 n_ind - ibd)."""
+    st = site_stats
+    num = np.asarray(st["n1"]) + 2 * np.asarray(st["n2"]) - np.asarray(st["alt_ibd"])
+    den = 2.0 * n_ind - np.asarray(st["ibd"])
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return np.where(den == 0, np.nan, num / np.where(den == 0, 1.0, den))
+
+
+def het_outside_ibd(region_stats):
+    """Heterozygosity outside IBD per (individual, region) from geno_smooth's region records:
+    het / non_ibd; NaN where non_ibd is 0."""
+    het, non = np.asarray(region_stats["het"]), np.asarray(region_stats["non_ibd"])
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return np.where(non == 0, np.nan, het / np.where(non == 0, 1.0, non))
 
 
 # nghmm_path_stats (include/nghmm.h): one record per (draw, individual) of sample_paths
@@ -1043,6 +1107,19 @@ class NgsFHMM:
         return _freq_info(lambda *a: self.lib.nghmm_freq_info(self._h, *a), self._check, self.n_ind,
                           self.n_sites, levels, cavity)
 
+    def geno_smooth(self, regions=None, sites=True, post=False, call=False):
+        """Genotype posteriors under the HMM, at the CURRENT indF, alpha and freq (nghmm_geno_smooth):
+        per cell P(genotype | all data of the individual), the IBD state of the site summed out
+        exactly.  Returns a dict of the arrays asked for: "regions" [I][R] of
+        GENO_REGION_STAT_DTYPE (het, het_prior, non_ibd, dosage summed over the sites of every
+        region; regions as ibd_summary takes them), "sites" [S] of GENO_SITE_STAT_DTYPE (n0, n1, n2,
+        het_prior, ibd, alt_ibd summed over the individuals), "post" [S][I][3] and "call" [S][I]
+        uint8 (3: no posterior).  geno_em_freq and het_outside_ibd turn the records into the exact
+        EM update of the frequencies and the heterozygosity outside IBD.  Conditional on indF,
+        alpha and the frequencies."""
+        return _geno_smooth(lambda *a: self.lib.nghmm_geno_smooth(self._h, *a), self._check, self.n_ind,
+                            self.n_sites, regions, sites, post, call)
+
     def obs_info(self, indF=None, alpha=None):
         """Per individual the log-likelihood, its gradient and its Hessian in (indF, alpha) under
         the current emissions, from exact derivatives (nghmm_obs_info): a structured array [I] of
@@ -1218,6 +1295,13 @@ class Chain:
         self._members_open()
         return _freq_info(lambda *a: self.lib.nghmm_chain_freq_info(self._arr, len(self.handles), *a),
                           self.handles[0]._check, self.n_ind, self.n_sites, levels, cavity)
+
+    def geno_smooth(self, regions=None, sites=True, post=False, call=False):
+        """NgsFHMM.geno_smooth over the chain (nghmm_chain_geno_smooth): global site indices, a
+        region across a shard boundary is one region."""
+        self._members_open()
+        return _geno_smooth(lambda *a: self.lib.nghmm_chain_geno_smooth(self._arr, len(self.handles), *a),
+                            self.handles[0]._check, self.n_ind, self.n_sites, regions, sites, post, call)
 
     def obs_info(self, indF=None, alpha=None):
         """NgsFHMM.obs_info over the chain (nghmm_chain_obs_info)."""
