@@ -783,6 +783,110 @@ int nghmm_chain_ibd_summary(nghmm_t** hs, int n, int what, double threshold, uin
                             const uint64_t* region_begin, const uint64_t* region_end,
                             nghmm_region_stat* regions, nghmm_site_stat* sites);
 
+/* ---- exact expectations over IBD paths: tracts, breakpoints, path entropy ----
+ * How many tracts an individual has, how long they are in Mb, where tract ends concentrate, and
+ * how uncertain the decode is as a whole -- exactly, where nghmm_sample_paths gives them by Monte
+ * Carlo with error 1 / sqrt(draws): closed-form sums of the posterior's pairwise marginals
+ * P(z_{s-1}, z_s | y), which the per-site posteriors (marginals of strongly dependent neighbours,
+ * and stored snapped to 0 / 1 within 1e-5) cannot give.  (The reference has no such function.)
+ *
+ * Definition.  At the handle's CURRENT parameters and emissions (as nghmm_tract_support and
+ * nghmm_sample_paths use them, not the last E-step's), for individual i, with f and beta the
+ * forward and backward vectors, T_s, q and c_s as in the sampler's definition above, e_s the
+ * emissions: for a site s that is NOT a chromosome start
+ *     m_s(k, l)  = T_s(k, l) e_s(l) beta_s(l)
+ *     n_s(k, l)  = f_{s-1}(k) m_s(k, l)
+ *     xi_s(k, l) = n_s(k, l) / sum_{k,l} n_s(k, l)            = P(z_{s-1} = k, z_s = l | y)
+ *     r_s(k, l)  = m_s(k, l) / (m_s(k, 0) + m_s(k, 1))        = P(z_s = l | z_{s-1} = k, y)
+ * and pi_s(l) = P(z_s = l | y) = xi_s(0, l) + xi_s(1, l), unsnapped.  Each of the four entries is
+ * formed from its own product, never as 1 - x; a common factor of the two emissions cancels.  At a
+ * chromosome start (d_s = +inf, and a handle's or chain's first site) T_s does not depend on k:
+ * z_s is independent of z_{s-1} given y, and the site contributes through pi_s alone.
+ *
+ *   term      not a chromosome start                     chromosome start
+ *   ibd_s     pi_s(1)                                    pi_s(1)
+ *   start_s   xi_s(0, 1)   (a tract begins at s)         pi_s(1)
+ *   on_s      xi_s(0, 1)                                 0
+ *   off_s     xi_s(1, 0)                                 0
+ *   mb_s      d_s xi_s(1, 1)                             0
+ *   h_s       -sum_{k,l} xi_s(k, l) ln r_s(k, l)         -sum_l pi_s(l) ln pi_s(l)
+ *   lp_s      ln r_s(z*_{s-1}, z*_s)                     ln pi_s(z*_s)
+ * mb_s is the expectation of the term nghmm_path_stats.ibd_mb adds; h_s uses 0 ln 0 = 0; lp_s is
+ * only formed with NGHMM_EXPECT_VITERBI, z* being the last nghmm_viterbi / nghmm_chain_viterbi
+ * decode of the loaded data.  The posterior is a Markov chain given y, so over all sites
+ *     sum start_s = E[n_tracts],  sum ibd_s = E[ibd_sites],  sum mb_s = E[ibd_mb]
+ * (nghmm_path_stats' definitions: tracts are cut at chromosome starts),
+ *     sum h_s = H(z | y), the entropy of the path posterior in nats,
+ *     sum lp_s = ln P(z* | y), the posterior probability of the decoded path itself.
+ * A state the data exclude (a heterozygote among called genotypes) makes its xi entries exactly 0;
+ * entropy terms with xi = 0 are 0; a 0/0 conditional counts as 0 as in nghmm_tract_support, so
+ * log_p_path may be -inf.  Nothing is ever NaN.
+ *
+ * regions [I][n_regions] (host): every field is the sum of the per-cell terms over the region's
+ * sites.  Regions are nghmm_ibd_summary's: half-open, sorted, disjoint, gaps allowed, handle-local
+ * indices for one handle and global for a chain.  EVERY site contributes its own term, a region's
+ * first site included, and that term looks at the site before it -- unlike vit_mb's rule, which
+ * leaves the step into a region's first site out.  So the records of regions that partition the
+ * data add up to the whole, and `starts` counts the tracts that BEGIN inside the region.
+ * sites [S] (host): each field is the sum over the individuals of on_s, off_s, ibd_s, h_s.
+ * regions is NULL iff n_regions == 0; sites may be NULL; at least one of the two is not.
+ *
+ * `what` is 0 or NGHMM_EXPECT_VITERBI (log_p_path is 0 without it).  NGHMM_ERR_ARG, with a
+ * message: the bit set and no decode since the load; an unknown bit; a handle without data; both
+ * outputs NULL, a NULL mismatch, unsorted, overlapping or empty regions, end > S.
+ *
+ * Evaluation and the order of every sum.  ln r comes from the small side: with x = min / max of
+ * the pair m(k, 0), m(k, 1), the larger entry's ln r is -log1p(x) and the smaller one's
+ * ln(x) - log1p(x) (both terms <= 0: no cancellation).  Exact mode: log1p(x) is u = 1 + x,
+ * u == 1 ? x : det_log(u) x / (u - 1).  Fast mode: log1p(x) = 2 atanh(x / (2 + x)) and ln(x) from
+ * the same odd series on the mantissa, both to relative accuracy (csrc/kernels_expect.hip).  So
+ * the entropy and log_p_path of an almost certain genome, sums of a million
+ * tiny terms of one sign, keep relative accuracy.  No float atomics.  Fast mode: a region is cut
+ * into pieces at the lane-chunk edges of the handle's layout (multiples of T sites,
+ * nghmm_fast_layout); within a piece the terms are added to 0 from the piece's LAST site to its
+ * first; the pieces are added in site order, the first one's value first.  Exact mode: one piece,
+ * from the region's last site to its first.  A site record: the individuals in blocks of 64; within
+ * a block (filled up with zeros) the butterfly x_i += x_{i ^ 32}, then ^ 16, 8, 4, 2, 1; the blocks
+ * in order, the first one's value first -- as nghmm_ibd_summary's post_sum.  The same bits on every
+ * call, and a region's record does not depend on which other regions or outputs are asked for.
+ * 
+ *
+ * Self-contained and read-only exactly like nghmm_tract_support: it refreshes stale emissions
+ * itself and leaves parameters, the posteriors of the last E-step, the Viterbi path, checkpoints
+ * and an M-step planned in advance untouched; an EM iteration after the call gives the bits it
+ * would have given without it.  Device scratch, kept by the handle: 48 bytes per (individual,
+ * piece) and (individual, region); and ONLY when sites is asked for, in a buffer of its own, the
+ * per-cell terms: 32 bytes per cell (individual x site, fast mode: x padded site)
+ * (NGHMM_ERR_NOMEM when it cannot be had). */
+enum { NGHMM_EXPECT_VITERBI = 1 };
+typedef struct nghmm_expect_region {  /* 48 bytes; one per (individual, region) */
+  double ibd;         /* sum ibd_s: expected sites in state IBD */
+  double starts;      /* sum start_s: expected number of tracts that begin in the region */
+  double switches;    /* sum on_s + off_s: expected number of state switches */
+  double ibd_mb;      /* sum mb_s: expected IBD length in Mb */
+  double entropy;     /* sum h_s, nats */
+  double log_p_path;  /* sum lp_s (0 without NGHMM_EXPECT_VITERBI; may be -inf) */
+} nghmm_expect_region;
+typedef struct nghmm_expect_site {    /* 32 bytes; one per site */
+  double on, off, ibd, entropy;  /* sums over the individuals of on_s, off_s, ibd_s, h_s */
+} nghmm_expect_site;
+#ifdef __cplusplus
+static_assert(sizeof(nghmm_expect_region) == 48 && sizeof(nghmm_expect_site) == 32, "record sizes");
+#endif
+int nghmm_ibd_expect(nghmm_t* h, int what, uint64_t n_regions, const uint64_t* region_begin,
+                     const uint64_t* region_end, nghmm_expect_region* regions,
+                     nghmm_expect_site* sites);
+/* The same over a chain of site shards (nghmm_chain_setup, else NGHMM_ERR_ARG): global site
+ * indices; the boundary vectors travel as in nghmm_chain_tract_support and the decoded state at a
+ * shard's last site as in nghmm_chain_ibd_summary; a region that crosses a shard boundary is one
+ * region, its shards' parts added on the host in rank order; sites [all sites] is the
+ * concatenation.  The results are within rounding of a single handle's, not its bytes: the
+ * lane-chunk grouping of a region's sum belongs to a handle's layout.  (Chains of more than one
+ * handle are fast mode only.) */
+int nghmm_chain_ibd_expect(nghmm_t** hs, int n_handles, int what, uint64_t n_regions,
+                           const uint64_t* region_begin, const uint64_t* region_end,
+                           nghmm_expect_region* regions, nghmm_expect_site* sites);
+
 /* ---- pairwise IBD sharing between individuals ----
  * How much IBD two individuals share over the sites [site_begin, site_end): three host matrices
  * [I][I], full and symmetric, reduced on the matrix cores from the decoded path and the

@@ -1,6 +1,6 @@
 // capi_internal.hpp -- what the translation units of the C ABI share: the handle, error plumbing,
 // and the helpers every entry point uses.  nghmm_capi.hip (handle life cycle, single-handle EM),
-// capi_load.hip (loaders), capi_output.hip (read-back and output formatting), capi_tracts.hip, capi_sample.hip, capi_info.hip, capi_summary.hip, capi_sharing.hip, capi_support.hip, capi_bounds.hip, capi_cavity.hip, capi_freqinfo.hip, capi_genosmooth.hip and
+// capi_load.hip (loaders), capi_output.hip (read-back and output formatting), capi_tracts.hip, capi_sample.hip, capi_info.hip, capi_summary.hip, capi_sharing.hip, capi_support.hip, capi_bounds.hip, capi_cavity.hip, capi_freqinfo.hip, capi_genosmooth.hip, capi_expect.hip and
 // capi_multi.hip (individual shards, site shards, groups and chains of handles) implement include/nghmm.h.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -121,6 +121,11 @@ struct nghmm_handle {
   // genotype posteriors under the HMM (capi_genosmooth.hip): the boundary vectors, the cavity
   // weights of every cell, the posteriors, the calls, the records and the pieces
   DevScratch<uint8_t> d_gsm;
+  // expectations over IBD paths (capi_expect.hip): the regions, their pieces and records, the
+  // boundary vectors, the site records; and, only when site records are asked for, the per-cell
+  // terms (32 bytes per cell) in an owner of their own
+  DevScratch<uint8_t> d_expt;
+  DevScratch<double> d_expt_cell;
   DevBuf<double> d_freq_new, d_hap;  // --freq_est 2 as intended: [S], [S][4]
 
   // multi-GPU shard

@@ -31,7 +31,11 @@
 // IBD state summed out exactly, raw doubles in the layout of PREFIX.geno), --geno_summary
 // [--geno_window N] (PREFIX.geno.regions and PREFIX.geno.sites: heterozygosity, also outside IBD,
 // and dosage per individual and chromosome or window of N sites; expected genotype counts and the
-// exact EM update of the frequency per site).
+// exact EM update of the frequency per site), --ibd_expect [--expect_window N] (PREFIX.ibd.expect:
+// per individual and chromosome or window of N sites the expected IBD sites, tracts, state switches
+// and Mb, the entropy of the path posterior and the posterior probability of the decoded path;
+// PREFIX.ibd.breaks: per site the expected individuals that enter and leave IBD; exact sums over
+// the posterior's pairwise marginals, made on the device after the final decode).
 // --n_threads (the reference's pool size) sets the host threads used for input normalisation and output
 // formatting; results do not depend on it.
 #include <fcntl.h>
@@ -71,6 +75,8 @@
 #pragma weak nghmm_chain_ibd_summary
 // ... and without the sharing entry: --ibd_sharing then stops with a message
 #pragma weak nghmm_chain_ibd_sharing
+// ... and without the expectation entry: --ibd_expect then stops with a message
+#pragma weak nghmm_chain_ibd_expect
 // ... and without the support entries: --ibd_support then stops with a message
 #pragma weak nghmm_tract_support
 #pragma weak nghmm_chain_tract_support
@@ -141,6 +147,12 @@ struct Params {  // ngsF-HMM.hpp:13-52
   // sites; --sharing_thresh P: the posterior threshold of its post_both column
   bool ibd_sharing = false;
   double sharing_thresh = 0.5;
+  // --ibd_expect: PREFIX.ibd.expect and PREFIX.ibd.breaks after the final decode
+  // (nghmm_chain_ibd_expect): exact expectations over IBD paths per individual and chromosome, or
+  // with --expect_window N per window of N sites that restarts at every chromosome start, and per
+  // site over the cohort
+  bool ibd_expect = false;
+  uint64_t expect_window = 0;
   // --ibd_support: PREFIX.ibd.support after the final decode -- per Viterbi tract the joint
   // posterior of IBD throughout, its log-odds against non-IBD throughout and the weakest site
   // (nghmm_chain_tract_support)
@@ -1522,6 +1534,73 @@ void write_ibd_summary(const Params& P, Cohort& C) {
   if (fclose(fh) != 0) fatal(__FUNCTION__, "cannot write the site summary output file!");
 }
 
+// PREFIX.ibd.expect: a header line, then per individual and region "IND_ID chr first_pos last_pos
+// n_sites exp_ibd_sites exp_tracts exp_switches exp_ibd_mb entropy log10_p_path" (tab-separated,
+// ordered by individual, then region; IDs, chromosome names and positions as --ibd_summary writes
+// them): the expected IBD sites, the expected number of tracts that begin in the region, of state
+// switches, the expected IBD length in Mb, the entropy of the path posterior (nats) and log10 of
+// the posterior probability of the decoded path's steps inside the region.  Regions are the
+// chromosomes, or windows of --expect_window sites that restart at every chromosome start.
+// PREFIX.ibd.breaks: a header line, then per site "chr pos on off ibd entropy": the expected
+// number of individuals that enter IBD at the site, that leave it, that are IBD, and the sum of
+// their entropy terms.  Doubles as %.10g, -inf as -inf; everything conditional on the final indF,
+// alpha and frequencies.
+void write_ibd_expect(const Params& P, Cohort& C) {
+  if (!nghmm_chain_ibd_expect)
+    fatal(__FUNCTION__, "--ibd_expect: the library has no nghmm_chain_ibd_expect!");
+  const uint64_t I = P.n_ind, S = P.n_sites;
+  std::vector<uint64_t> begin, end;
+  std::vector<size_t> chrom;   // the chromosome run of every region
+  for (size_t c = 0; c < P.chrom_first.size(); c++) {
+    const uint64_t a = P.chrom_first[c], b = c + 1 < P.chrom_first.size() ? P.chrom_first[c + 1] : S;
+    const uint64_t w = P.expect_window ? P.expect_window : b - a;
+    for (uint64_t lo = a; lo < b; lo += w) {
+      begin.push_back(lo);
+      end.push_back(b - lo < w ? b : lo + w);
+      chrom.push_back(c);
+    }
+  }
+  const uint64_t R = begin.size();
+  std::vector<nghmm_expect_region> reg((size_t)I * R);
+  std::vector<nghmm_expect_site> sites(S);
+  check(nghmm_chain_ibd_expect(C.hs.data(), C.n(), NGHMM_EXPECT_VITERBI, R, begin.data(), end.data(),
+                               reg.data(), sites.data()),
+        "ibd_expect");
+  std::string name = P.prefix + ".ibd.expect";
+  FILE* fh = fopen(name.c_str(), "w");
+  if (!fh) fatal(__FUNCTION__, "cannot open path expectation output file!");
+  setvbuf(fh, nullptr, _IOFBF, 1 << 22);
+  fputs("ind\tchr\tfirst_pos\tlast_pos\tn_sites\texp_ibd_sites\texp_tracts\texp_switches\texp_ibd_mb\t"
+        "entropy\tlog10_p_path\n", fh);
+  const double ln10 = 2.302585092994045684;
+  for (uint64_t i = 0; i < I; i++) {
+    const std::string id = P.ind_names.empty() ? "ind" + std::to_string(i) : P.ind_names[i];
+    for (uint64_t r = 0; r < R; r++) {
+      const nghmm_expect_region& t = reg[i * R + r];
+      fprintf(fh, "%s\t%s\t%llu\t%llu\t%llu\t%.10g\t%.10g\t%.10g\t%.10g\t%.10g\t", id.c_str(),
+              P.chrom_name[chrom[r]].c_str(), (unsigned long long)P.site_pos[begin[r]],
+              (unsigned long long)P.site_pos[end[r] - 1], (unsigned long long)(end[r] - begin[r]), t.ibd,
+              t.starts, t.switches, t.ibd_mb, t.entropy);
+      if (t.log_p_path == -HUGE_VAL) fputs("-inf\n", fh);
+      else fprintf(fh, "%.10g\n", t.log_p_path / ln10);
+    }
+  }
+  if (fclose(fh) != 0) fatal(__FUNCTION__, "cannot write the path expectation output file!");
+  name = P.prefix + ".ibd.breaks";
+  fh = fopen(name.c_str(), "w");
+  if (!fh) fatal(__FUNCTION__, "cannot open breakpoint output file!");
+  setvbuf(fh, nullptr, _IOFBF, 1 << 22);
+  fputs("chr\tpos\ton\toff\tibd\tentropy\n", fh);
+  size_t c = 0;
+  for (uint64_t s = 0; s < S; s++) {
+    while (c + 1 < P.chrom_first.size() && P.chrom_first[c + 1] <= s) c++;
+    const nghmm_expect_site& t = sites[s];
+    fprintf(fh, "%s\t%llu\t%.10g\t%.10g\t%.10g\t%.10g\n", P.chrom_name[c].c_str(),
+            (unsigned long long)P.site_pos[s], t.on, t.off, t.ibd, t.entropy);
+  }
+  if (fclose(fh) != 0) fatal(__FUNCTION__, "cannot write the breakpoint output file!");
+}
+
 // PREFIX.ibd.sharing: a header line, then per pair of individuals i <= j, in (i, j) order,
 // "IND_ID1 IND_ID2 vit_both post_both post_prod" (tab-separated; IDs as --ibd_bed names them): the
 // sites, genome-wide, at which both are IBD in the decoded path, at which both posteriors reach
@@ -1843,6 +1922,7 @@ void parse_cmd_args(Params& P, int argc, char** argv) {  // parse_args.cpp:41-22
       {"freq_info", no_argument, nullptr, 1025},      {"freq_levels", required_argument, nullptr, 1026},
       {"geno_smooth", no_argument, nullptr, 1027},    {"geno_summary", no_argument, nullptr, 1028},
       {"geno_window", required_argument, nullptr, 1029},
+      {"ibd_expect", no_argument, nullptr, 1030},     {"expect_window", required_argument, nullptr, 1031},
       {0, 0, 0, 0}};
   long taus_kat = 0;
   bool parse_kat = false, se_kat = false;
@@ -1899,6 +1979,11 @@ void parse_cmd_args(Params& P, int argc, char** argv) {  // parse_args.cpp:41-22
       case 1029:
         if (atoll(optarg) < 1) fatal(__FUNCTION__, "invalid --geno_window (sites per window)!");
         P.geno_window = strtoull(optarg, nullptr, 10);
+        break;
+      case 1030: P.ibd_expect = true; break;
+      case 1031:
+        if (atoll(optarg) < 1) fatal(__FUNCTION__, "invalid --expect_window (sites per window)!");
+        P.expect_window = strtoull(optarg, nullptr, 10);
         break;
       case 1026: {   // a,b,...: every field a number in [0, 1]
         P.freq_levels.clear();
@@ -2030,6 +2115,9 @@ void parse_cmd_args(Params& P, int argc, char** argv) {  // parse_args.cpp:41-22
   if ((P.geno_smooth || P.geno_summary) && !nghmm_chain_geno_smooth)
     fatal(__FUNCTION__, "--geno_smooth / --geno_summary: the library has no nghmm_chain_geno_smooth!");
   if (!P.geno_summary && P.geno_window) warn(__FUNCTION__, "--geno_window is only used by --geno_summary");
+  if (P.ibd_expect && !nghmm_chain_ibd_expect)
+    fatal(__FUNCTION__, "--ibd_expect: the library has no nghmm_chain_ibd_expect!");
+  if (!P.ibd_expect && P.expect_window) warn(__FUNCTION__, "--expect_window is only used by --ibd_expect");
   if (P.min_iters < 1 || P.max_iters < 1 || P.min_iters >= P.max_iters)
     fatal(__FUNCTION__, "invalid number of iterations!");
   if (P.n_threads < 1) fatal(__FUNCTION__, "invalid number of threads!");
@@ -2062,8 +2150,8 @@ void parse_cmd_args(Params& P, int argc, char** argv) {  // parse_args.cpp:41-22
     if (P.ind_names.size() != P.n_ind)
       fatal(__FUNCTION__, "number of lines in --ind_names file is not --n_ind!");
     if (!P.ibd_bed && !P.sample_paths && !P.indF_se && !P.ibd_summary && !P.ibd_sharing && !P.ibd_support &&
-        !P.ibd_bounds && !P.geno_summary)
-      warn(__FUNCTION__, "--ind_names is only used by --ibd_bed, --sample_paths, --indF_se, --ibd_summary, --ibd_sharing, --ibd_support, --ibd_bounds and --geno_summary");
+        !P.ibd_bounds && !P.geno_summary && !P.ibd_expect)
+      warn(__FUNCTION__, "--ind_names is only used by --ibd_bed, --sample_paths, --indF_se, --ibd_summary, --ibd_sharing, --ibd_support, --ibd_bounds, --geno_summary and --ibd_expect");
   }
   P.prefix = P.out_prefix;
 }
@@ -2164,6 +2252,7 @@ void finish_run(Params& P, Cohort& C) {
   if (P.ibd_bounds) write_ibd_bounds(P, C);
   if (P.freq_info) write_freq_info(P, C);
   if (P.geno_smooth || P.geno_summary) write_geno_smooth(P, C);
+  if (P.ibd_expect) write_ibd_expect(P, C);
   if (P.verbose >= 2)  // (not a line of the reference's)
     fprintf(P.out, "> decoded in %.2f s, output files written in %.2f s\n", t1 - t0, omp_get_wtime() - t1);
 }
@@ -2284,6 +2373,7 @@ int main(int argc, char** argv) {
         runs[r].freq_info = P.freq_info && r == best;
         runs[r].geno_smooth = P.geno_smooth && r == best;
         runs[r].geno_summary = P.geno_summary && r == best;
+        runs[r].ibd_expect = P.ibd_expect && r == best;
         finish_run(runs[r], cs[r]);
       }
       fclose(runs[r].out);
@@ -2308,6 +2398,10 @@ int main(int argc, char** argv) {
       if (P.geno_summary) {
         exts.push_back(".geno.regions");
         exts.push_back(".geno.sites");
+      }
+      if (P.ibd_expect) {
+        exts.push_back(".ibd.expect");
+        exts.push_back(".ibd.breaks");
       }
       for (unsigned k = 1; P.sample_paths && k <= P.sample_keep; k++) {
         char tag[32];

@@ -164,6 +164,9 @@ def load_library():
         "nghmm_ibd_sharing": (i32, [vp, i32, d, u64, u64, C.POINTER(u64), C.POINTER(u64), dp]),
         "nghmm_chain_ibd_sharing": (i32, [C.POINTER(vp), i32, i32, d, u64, u64, C.POINTER(u64),
                                           C.POINTER(u64), dp]),
+        "nghmm_ibd_expect": (i32, [vp, i32, u64, C.POINTER(u64), C.POINTER(u64), vp, vp]),
+        "nghmm_chain_ibd_expect": (i32, [C.POINTER(vp), i32, i32, u64, C.POINTER(u64), C.POINTER(u64),
+                                         vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -208,6 +211,7 @@ EXPORTED_SYMBOLS = [
     "nghmm_obs_info", "nghmm_chain_obs_info",
     "nghmm_ibd_summary", "nghmm_chain_ibd_summary",
     "nghmm_ibd_sharing", "nghmm_chain_ibd_sharing",
+    "nghmm_ibd_expect", "nghmm_chain_ibd_expect",
 ]
 
 OBJECTIVE_FN = C.CFUNCTYPE(C.c_double, C.c_uint32, C.c_double, C.c_double, C.c_void_p)
@@ -604,6 +608,59 @@ def _ibd_summary(call, check, n_ind, n_sites, regions, what, threshold, sites):
                C.c_void_p(region_stats.ctypes.data) if R else None,
                C.c_void_p(site_stats.ctypes.data) if sites else None))
     return region_stats, site_stats
+
+
+EXPECT_VITERBI = 1     # nghmm_ibd_expect: also the posterior probability of the decoded path
+
+
+class ExpectRegion(C.Structure):     # nghmm_expect_region (include/nghmm.h)
+    _fields_ = [(n, C.c_double) for n in ("ibd", "starts", "switches", "ibd_mb", "entropy",
+                                          "log_p_path")]
+
+
+class ExpectSite(C.Structure):       # nghmm_expect_site (include/nghmm.h)
+    _fields_ = [(n, C.c_double) for n in ("on", "off", "ibd", "entropy")]
+
+
+EXPECT_REGION_DTYPE = np.dtype([(n, np.float64) for n, _ in ExpectRegion._fields_])
+EXPECT_SITE_DTYPE = np.dtype([(n, np.float64) for n, _ in ExpectSite._fields_])
+assert EXPECT_REGION_DTYPE.itemsize == C.sizeof(ExpectRegion) == 48
+assert EXPECT_SITE_DTYPE.itemsize == C.sizeof(ExpectSite) == 32
+
+
+def _ibd_expect(call, check, n_ind, n_sites, regions, sites, viterbi):
+    u64p = C.POINTER(C.c_uint64)
+    if regions is None:
+        reg = np.array([[0, n_sites]], dtype=np.uint64)
+    else:
+        reg = np.asarray(regions)
+        if reg.size == 0:
+            reg = reg.reshape(0, 2)
+        if reg.ndim != 2 or reg.shape[1] != 2 or not np.issubdtype(reg.dtype, np.integer) or \
+                (reg < 0).any():
+            raise NgsFHMMError(-10, "ibd_expect: regions is an [R][2] array of site indices "
+                                    "(begin, end)")
+        reg = reg.astype(np.uint64)
+    R = len(reg)
+    begin, end = np.ascontiguousarray(reg[:, 0]), np.ascontiguousarray(reg[:, 1])
+    region_stats = np.zeros((n_ind, R), dtype=EXPECT_REGION_DTYPE) if R else None
+    site_stats = np.zeros(n_sites, dtype=EXPECT_SITE_DTYPE) if sites else None
+    check(call(EXPECT_VITERBI if viterbi else 0, R,
+               begin.ctypes.data_as(u64p) if R else None, end.ctypes.data_as(u64p) if R else None,
+               C.c_void_p(region_stats.ctypes.data) if R else None,
+               C.c_void_p(site_stats.ctypes.data) if sites else None))
+    return region_stats, site_stats
+
+
+def expect_tract_length(region_stats):
+    """(sites, mb) of ibd_expect's region records: the expected IBD sites per expected tract and
+    the expected Mb per expected tract, NaN where `starts` is 0."""
+    st = np.asarray(region_stats["starts"], dtype=np.float64)
+    sites = np.full(st.shape, np.nan)
+    mb = np.full(st.shape, np.nan)
+    np.divide(region_stats["ibd"], st, out=sites, where=st != 0)
+    np.divide(region_stats["ibd_mb"], st, out=mb, where=st != 0)
+    return sites, mb
 
 
 SHARING_VITERBI = 1    # nghmm_ibd_sharing sources, a bit mask (include/nghmm.h)
@@ -1139,6 +1196,15 @@ class NgsFHMM:
         return _ibd_summary(lambda *a: self.lib.nghmm_ibd_summary(self._h, *a), self._check,
                             self.n_ind, self.n_sites, regions, what, threshold, sites)
 
+    def ibd_expect(self, regions=None, sites=True, viterbi=False):
+        """Exact expectations over IBD paths (nghmm_ibd_expect): (region_stats, site_stats), the
+        first [I][R] of EXPECT_REGION_DTYPE (ibd, starts, switches, ibd_mb, entropy, log_p_path;
+        regions as ibd_summary takes them, None = one region over all sites), the second [S] of
+        EXPECT_SITE_DTYPE (on, off, ibd, entropy; None unless sites).  viterbi: also the log
+        posterior probability of the last decoded path (log_p_path, else 0)."""
+        return _ibd_expect(lambda *a: self.lib.nghmm_ibd_expect(self._h, *a), self._check,
+                           self.n_ind, self.n_sites, regions, sites, viterbi)
+
     def ibd_sharing(self, what=("viterbi", "posterior"), threshold=0.5, site_begin=0, site_end=None):
         """Pairwise IBD sharing over the sites [site_begin, site_end) (default: all), reduced on
         the matrix cores (nghmm_ibd_sharing).  what: "viterbi" (vit_both, from the last decode),
@@ -1316,6 +1382,14 @@ class Chain:
         return _ibd_summary(
             lambda *a: self.lib.nghmm_chain_ibd_summary(self._arr, len(self.handles), *a),
             self.handles[0]._check, self.n_ind, self.n_sites, regions, what, threshold, sites)
+
+    def ibd_expect(self, regions=None, sites=True, viterbi=False):
+        """NgsFHMM.ibd_expect over the chain (nghmm_chain_ibd_expect): global site indices, a region
+        across a shard boundary is one region; within rounding of a single handle's values."""
+        self._members_open()
+        return _ibd_expect(
+            lambda *a: self.lib.nghmm_chain_ibd_expect(self._arr, len(self.handles), *a),
+            self.handles[0]._check, self.n_ind, self.n_sites, regions, sites, viterbi)
 
     def ibd_sharing(self, what=("viterbi", "posterior"), threshold=0.5, site_begin=0, site_end=None):
         """NgsFHMM.ibd_sharing over the chain (nghmm_chain_ibd_sharing): global site indices, the
