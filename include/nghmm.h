@@ -887,6 +887,102 @@ int nghmm_chain_ibd_expect(nghmm_t** hs, int n_handles, int what, uint64_t n_reg
                            const uint64_t* region_begin, const uint64_t* region_end,
                            nghmm_expect_region* regions, nghmm_expect_site* sites);
 
+/* ---- exact posterior variances of IBD share and tract count per region ----
+ * nghmm_ibd_expect gives the posterior MEANS of the summaries people publish (F_ROH of a genome, a
+ * chromosome or a window, the number of tracts, the IBD length in Mb); this call gives their
+ * posterior covariance matrix as well, exactly, where nghmm_sample_paths estimates a variance from
+ * R draws with relative error about sqrt(2 / R).  (The reference has no such function.)
+ *
+ * Definition.  At the handle's CURRENT parameters and emissions, as nghmm_ibd_expect; T_s, q, c_s,
+ * e_s, the forward vector f, the backward vector beta and what counts as a chromosome start
+ * (d_s = +inf, or the first site of a handle or chain) are those of the sampler's and
+ * nghmm_ibd_expect's definitions above.  Every step (z_{s-1} = k, z_s = l) contributes
+ *
+ *   statistic            not a chromosome start     chromosome start
+ *   sites  phiN_s(k, l)  [l = 1]                    [l = 1]
+ *   tracts phiT_s(k, l)  [k = 0, l = 1]             [l = 1]
+ *   Mb     phiL_s(k, l)  d_s [k = 1, l = 1]         0
+ *
+ * -- exactly the terms nghmm_path_stats adds to a path's ibd_sites, n_tracts and ibd_mb.  For a
+ * region R = [a, b):  A_R = sum_{s in R} phiA_s(z_{s-1}, z_s) with A = N, or A = L with the flag
+ * NGHMM_MOMENTS_MB, and T_R = sum_{s in R} phiT_s.  As in nghmm_ibd_expect EVERY site contributes
+ * its own term, a region's first site included, and that term looks at the site before it.  With
+ * M_s = T_s diag(e_s), the tilted product
+ *     Z_R(t) = f_{a-1} [prod_{s=a}^{b-1} M_s o exp(t_A phiA_s + t_T phiT_s)] beta_{b-1}
+ * (o entrywise; f_{a-1} = q for a = 0 or the chain's first site, beta = 1 behind the last site; f
+ * and beta at t = 0, at any scale) is the moment generating function of (A_R, T_R) given y times a
+ * constant, so the gradient of log Z_R at 0 is their posterior mean and the Hessian their
+ * posterior covariance matrix -- both exactly:
+ *     mean_a = d_A log Z_R(0)  = E[A_R | y]       (nghmm_ibd_expect's `ibd` or `ibd_mb`)
+ *     mean_t = d_T log Z_R(0)  = E[T_R | y]       (nghmm_ibd_expect's `starts`)
+ *     var_a  = d_AA log Z_R(0) = Var(A_R | y)     (a value that rounds below 0 is returned as 0)
+ *     cov_at = d_AT log Z_R(0) = Cov(A_R, T_R | y)
+ *     var_t  = d_TT log Z_R(0) = Var(T_R | y)     (the same clamp)
+ * **Everything is conditional on indF, alpha and the allele frequencies**, as the results of the
+ * other calls are: the uncertainty of the parameters (nghmm_obs_info) is not in these variances.
+ * A state the data exclude gives exact zeros where it should (a one-site region on an excluded
+ * state has variance exactly 0); nothing is ever NaN.  A one-site region has mean_a = pi_s(1) and
+ * var_a = pi_s(1) pi_s(0) with A = sites.  The operator at a chromosome start has rank one, so
+ * chromosomes are independent given the parameters: the variances and covariances of regions that
+ * are whole chromosomes add up to those of the whole data.
+ *
+ * regions [I][n_regions] (host).  Regions are nghmm_ibd_summary's: half-open, sorted, disjoint,
+ * gaps allowed, handle-local indices for one handle and global for a chain; they may span
+ * chromosome starts.  NGHMM_ERR_ARG, with a message: an unknown bit in `what`; a handle without
+ * data; n_regions == 0; a NULL pointer; unsorted, overlapping or empty regions; end > S.
+ *
+ * Evaluation and the order of operations.  The t-derivatives of a tilted site are entrywise masks
+ * of M_s, so the product rule to second order in (t_A, t_T) is the jet algebra of nghmm_obs_info
+ * (six 2x2 matrices, one exponent).  A plain jet loses digits when it is closed -- Z_AA / Z -
+ * (Z_A / Z)^2 cancels like eps E[A]^2 / Var, half the digits at 10^6 sites -- so every partial
+ * product carries an offset pair next to its jet and stores the jet of the statistics MINUS the
+ * offsets; a product adds the offsets and re-centres them by (sum of the entries of V_a) / (sum of
+ * the entries of V) wherever it rescales; closing gives mean = offset + Z_a / Z and the
+ * covariances unchanged.  Fast mode: the site axis is partitioned by the region edges into
+ * segments (the regions and the gaps, at most 2 n_regions + 1) and the segments at the lane-chunk
+ * edges of the layout (multiples of T sites, nghmm_fast_layout) into pieces; a lane multiplies its
+ * sites in order, rescaling and re-centring every 8; a wave of 64 lane-chunks that lies in one
+ * segment multiplies its lanes in an ordered tree into one piece; a segment's pieces are
+ * multiplied in runs of ceil(n / 64) consecutive pieces and the runs in an ordered tree; then per
+ * individual the backward vectors from the last segment to the first and the forward vectors from
+ * the first to the last through the segments' value components, each scaled to sum 1, closing
+ * every region on the way.  Exact mode: per individual a backward pass that keeps beta at the
+ * region ends, then a forward pass that carries f times the region's centred jet, rescaled and
+ * re-centred every 8 sites, and closes at the region's end.  No float atomics: the same arguments
+ * give the same bits on every call.  UNLIKE nghmm_ibd_expect, a region's record may depend in its
+ * last bits on which other regions are asked for (f and beta come from the other segments'
+ * products); it agrees within rounding.  
+ *
+ * Self-contained and read-only exactly like nghmm_ibd_expect: it refreshes stale emissions itself
+ * and leaves parameters, the posteriors of the last E-step, the Viterbi path, checkpoints and an
+ * M-step planned in advance untouched; an EM iteration after the call gives the bits it would
+ * have given without it.  Device scratch, kept by the handle (NGHMM_ERR_NOMEM when it cannot be
+ * had): fast mode 216 bytes per (individual, piece) -- pieces <= 64 C + 2 n_regions + 1, and C +
+ * 2 n_regions + 1 when no region edge falls inside a wave --, 232 bytes per (individual, segment),
+ * 40 per (individual, region) and tables of 4 bytes per lane-chunk and 8 per piece; exact mode 56
+ * bytes per (individual, region). */
+enum { NGHMM_MOMENTS_MB = 1 };
+typedef struct nghmm_moment_region {  /* 40 bytes; one per (individual, region) */
+  double mean_a;  /* E[A_R | y]: expected IBD sites (or Mb with NGHMM_MOMENTS_MB) */
+  double mean_t;  /* E[T_R | y]: expected number of tracts that begin in the region */
+  double var_a;   /* Var(A_R | y), >= 0 */
+  double cov_at;  /* Cov(A_R, T_R | y) */
+  double var_t;   /* Var(T_R | y), >= 0 */
+} nghmm_moment_region;
+#ifdef __cplusplus
+static_assert(sizeof(nghmm_moment_region) == 40, "record size");
+#endif
+int nghmm_ibd_moments(nghmm_t* h, int what, uint64_t n_regions, const uint64_t* region_begin,
+                      const uint64_t* region_end, nghmm_moment_region* regions);
+/* The same over a chain of site shards (nghmm_chain_setup, else NGHMM_ERR_ARG): global site
+ * indices.  Each shard reduces its site range to the centred jets of its parts of the segments;
+ * the host multiplies the parts of a segment across the cuts in rank order with the routine the
+ * device uses, then scans and closes once.  The results are within rounding of a single handle's,
+ * not its bytes.  (Chains of more than one handle are fast mode only.) */
+int nghmm_chain_ibd_moments(nghmm_t** hs, int n_handles, int what, uint64_t n_regions,
+                            const uint64_t* region_begin, const uint64_t* region_end,
+                            nghmm_moment_region* regions);
+
 /* ---- pairwise IBD sharing between individuals ----
  * How much IBD two individuals share over the sites [site_begin, site_end): three host matrices
  * [I][I], full and symmetric, reduced on the matrix cores from the decoded path and the

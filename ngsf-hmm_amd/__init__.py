@@ -23,7 +23,8 @@ from .hmm import (NgsFHMM, NgsFHMMError, Group, Chain, MODE_EXACT, MODE_FAST, GE
                   sharing_splits, sharing_jaccard, TractScore, TRACT_SCORE_DTYPE, TractBound,
                   TRACT_BOUND_DTYPE, NO_ANCHOR, FREQ_STAT_DTYPE, freq_std_errors,
                   GENO_SITE_STAT_DTYPE, GENO_REGION_STAT_DTYPE, geno_em_freq, het_outside_ibd,
-                  EXPECT_VITERBI, EXPECT_REGION_DTYPE, EXPECT_SITE_DTYPE, expect_tract_length)
+                  EXPECT_VITERBI, EXPECT_REGION_DTYPE, EXPECT_SITE_DTYPE, expect_tract_length,
+                  MOMENTS_MB, MOMENT_REGION_DTYPE, moment_sd)
 from . import simulate
 
 __all__ = ["NgsFHMM", "NgsFHMMError", "Group", "Chain", "MODE_EXACT", "MODE_FAST", "GENO_PACKED", "LD_INTENDED", "EPROB_LD", "library_path",
@@ -35,4 +36,5 @@ __all__ = ["NgsFHMM", "NgsFHMMError", "Group", "Chain", "MODE_EXACT", "MODE_FAST
            "TRACT_SCORE_DTYPE", "TractBound", "TRACT_BOUND_DTYPE", "NO_ANCHOR",
            "FREQ_STAT_DTYPE", "freq_std_errors", "GENO_SITE_STAT_DTYPE", "GENO_REGION_STAT_DTYPE",
            "geno_em_freq", "het_outside_ibd", "EXPECT_VITERBI", "EXPECT_REGION_DTYPE",
-           "EXPECT_SITE_DTYPE", "expect_tract_length"]
+           "EXPECT_SITE_DTYPE", "expect_tract_length", "MOMENTS_MB", "MOMENT_REGION_DTYPE",
+           "moment_sd"]

@@ -35,7 +35,11 @@
 // per individual and chromosome or window of N sites the expected IBD sites, tracts, state switches
 // and Mb, the entropy of the path posterior and the posterior probability of the decoded path;
 // PREFIX.ibd.breaks: per site the expected individuals that enter and leave IBD; exact sums over
-// the posterior's pairwise marginals, made on the device after the final decode).
+// the posterior's pairwise marginals, made on the device after the final decode),
+// --ibd_moments [--moments_window N] (PREFIX.ibd.moments: per individual and chromosome or window
+// of N sites the exact posterior mean and standard deviation of the IBD sites, of the number of
+// tracts and of the IBD length in Mb, and their correlations, made on the device after the final
+// decode).
 // --n_threads (the reference's pool size) sets the host threads used for input normalisation and output
 // formatting; results do not depend on it.
 #include <fcntl.h>
@@ -77,6 +81,8 @@
 #pragma weak nghmm_chain_ibd_sharing
 // ... and without the expectation entry: --ibd_expect then stops with a message
 #pragma weak nghmm_chain_ibd_expect
+// ... and without the moments entry: --ibd_moments then stops with a message
+#pragma weak nghmm_chain_ibd_moments
 // ... and without the support entries: --ibd_support then stops with a message
 #pragma weak nghmm_tract_support
 #pragma weak nghmm_chain_tract_support
@@ -153,6 +159,12 @@ struct Params {  // ngsF-HMM.hpp:13-52
   // site over the cohort
   bool ibd_expect = false;
   uint64_t expect_window = 0;
+  // --ibd_moments: PREFIX.ibd.moments after the final decode (nghmm_chain_ibd_moments): the exact
+  // posterior means, standard deviations and correlations of IBD sites, tracts and IBD Mb per
+  // individual and chromosome, or with --moments_window N per window of N sites that restarts at
+  // every chromosome start
+  bool ibd_moments = false;
+  uint64_t moments_window = 0;
   // --ibd_support: PREFIX.ibd.support after the final decode -- per Viterbi tract the joint
   // posterior of IBD throughout, its log-odds against non-IBD throughout and the weakest site
   // (nghmm_chain_tract_support)
@@ -1601,6 +1613,60 @@ void write_ibd_expect(const Params& P, Cohort& C) {
   if (fclose(fh) != 0) fatal(__FUNCTION__, "cannot write the breakpoint output file!");
 }
 
+// PREFIX.ibd.moments: a header line, then per individual and region "ind chr first_pos last_pos
+// n_sites exp_ibd_sites sd_ibd_sites exp_tracts sd_tracts corr_sites_tracts exp_ibd_mb sd_ibd_mb
+// corr_mb_tracts" (tab-separated, ordered by individual, then region; IDs, chromosome names,
+// positions and regions as --ibd_expect writes them, with --moments_window for the windows): the
+// exact posterior mean and standard deviation of the IBD sites, of the number of tracts that begin
+// in the region and of the IBD length in Mb, and the posterior correlations of the two lengths
+// with the number of tracts -- two calls, one per length.  Doubles as %.10g, a correlation with a
+// variance of 0 as NA; everything conditional on the final indF, alpha and frequencies.
+void write_ibd_moments(const Params& P, Cohort& C) {
+  if (!nghmm_chain_ibd_moments)
+    fatal(__FUNCTION__, "--ibd_moments: the library has no nghmm_chain_ibd_moments!");
+  const uint64_t I = P.n_ind, S = P.n_sites;
+  std::vector<uint64_t> begin, end;
+  std::vector<size_t> chrom;   // the chromosome run of every region
+  for (size_t c = 0; c < P.chrom_first.size(); c++) {
+    const uint64_t a = P.chrom_first[c], b = c + 1 < P.chrom_first.size() ? P.chrom_first[c + 1] : S;
+    const uint64_t w = P.moments_window ? P.moments_window : b - a;
+    for (uint64_t lo = a; lo < b; lo += w) {
+      begin.push_back(lo);
+      end.push_back(b - lo < w ? b : lo + w);
+      chrom.push_back(c);
+    }
+  }
+  const uint64_t R = begin.size();
+  std::vector<nghmm_moment_region> ns((size_t)I * R), mb((size_t)I * R);
+  check(nghmm_chain_ibd_moments(C.hs.data(), C.n(), 0, R, begin.data(), end.data(), ns.data()), "ibd_moments");
+  check(nghmm_chain_ibd_moments(C.hs.data(), C.n(), NGHMM_MOMENTS_MB, R, begin.data(), end.data(), mb.data()),
+        "ibd_moments");
+  const std::string name = P.prefix + ".ibd.moments";
+  FILE* fh = fopen(name.c_str(), "w");
+  if (!fh) fatal(__FUNCTION__, "cannot open posterior moments output file!");
+  setvbuf(fh, nullptr, _IOFBF, 1 << 22);
+  fputs("ind\tchr\tfirst_pos\tlast_pos\tn_sites\texp_ibd_sites\tsd_ibd_sites\texp_tracts\tsd_tracts\t"
+        "corr_sites_tracts\texp_ibd_mb\tsd_ibd_mb\tcorr_mb_tracts\n", fh);
+  auto corr = [fh](const nghmm_moment_region& t, char sep) {
+    if (t.var_a > 0 && t.var_t > 0) fprintf(fh, "%.10g%c", t.cov_at / (sqrt(t.var_a) * sqrt(t.var_t)), sep);
+    else fprintf(fh, "NA%c", sep);
+  };
+  for (uint64_t i = 0; i < I; i++) {
+    const std::string id = P.ind_names.empty() ? "ind" + std::to_string(i) : P.ind_names[i];
+    for (uint64_t r = 0; r < R; r++) {
+      const nghmm_moment_region &t = ns[i * R + r], &u = mb[i * R + r];
+      fprintf(fh, "%s\t%s\t%llu\t%llu\t%llu\t%.10g\t%.10g\t%.10g\t%.10g\t", id.c_str(),
+              P.chrom_name[chrom[r]].c_str(), (unsigned long long)P.site_pos[begin[r]],
+              (unsigned long long)P.site_pos[end[r] - 1], (unsigned long long)(end[r] - begin[r]), t.mean_a,
+              sqrt(t.var_a), t.mean_t, sqrt(t.var_t));
+      corr(t, '\t');
+      fprintf(fh, "%.10g\t%.10g\t", u.mean_a, sqrt(u.var_a));
+      corr(u, '\n');
+    }
+  }
+  if (fclose(fh) != 0) fatal(__FUNCTION__, "cannot write the posterior moments output file!");
+}
+
 // PREFIX.ibd.sharing: a header line, then per pair of individuals i <= j, in (i, j) order,
 // "IND_ID1 IND_ID2 vit_both post_both post_prod" (tab-separated; IDs as --ibd_bed names them): the
 // sites, genome-wide, at which both are IBD in the decoded path, at which both posteriors reach
@@ -1923,6 +1989,7 @@ void parse_cmd_args(Params& P, int argc, char** argv) {  // parse_args.cpp:41-22
       {"geno_smooth", no_argument, nullptr, 1027},    {"geno_summary", no_argument, nullptr, 1028},
       {"geno_window", required_argument, nullptr, 1029},
       {"ibd_expect", no_argument, nullptr, 1030},     {"expect_window", required_argument, nullptr, 1031},
+      {"ibd_moments", no_argument, nullptr, 1032},    {"moments_window", required_argument, nullptr, 1033},
       {0, 0, 0, 0}};
   long taus_kat = 0;
   bool parse_kat = false, se_kat = false;
@@ -1984,6 +2051,11 @@ void parse_cmd_args(Params& P, int argc, char** argv) {  // parse_args.cpp:41-22
       case 1031:
         if (atoll(optarg) < 1) fatal(__FUNCTION__, "invalid --expect_window (sites per window)!");
         P.expect_window = strtoull(optarg, nullptr, 10);
+        break;
+      case 1032: P.ibd_moments = true; break;
+      case 1033:
+        if (atoll(optarg) < 1) fatal(__FUNCTION__, "invalid --moments_window (sites per window)!");
+        P.moments_window = strtoull(optarg, nullptr, 10);
         break;
       case 1026: {   // a,b,...: every field a number in [0, 1]
         P.freq_levels.clear();
@@ -2118,6 +2190,9 @@ void parse_cmd_args(Params& P, int argc, char** argv) {  // parse_args.cpp:41-22
   if (P.ibd_expect && !nghmm_chain_ibd_expect)
     fatal(__FUNCTION__, "--ibd_expect: the library has no nghmm_chain_ibd_expect!");
   if (!P.ibd_expect && P.expect_window) warn(__FUNCTION__, "--expect_window is only used by --ibd_expect");
+  if (P.ibd_moments && !nghmm_chain_ibd_moments)
+    fatal(__FUNCTION__, "--ibd_moments: the library has no nghmm_chain_ibd_moments!");
+  if (!P.ibd_moments && P.moments_window) warn(__FUNCTION__, "--moments_window is only used by --ibd_moments");
   if (P.min_iters < 1 || P.max_iters < 1 || P.min_iters >= P.max_iters)
     fatal(__FUNCTION__, "invalid number of iterations!");
   if (P.n_threads < 1) fatal(__FUNCTION__, "invalid number of threads!");
@@ -2150,8 +2225,8 @@ void parse_cmd_args(Params& P, int argc, char** argv) {  // parse_args.cpp:41-22
     if (P.ind_names.size() != P.n_ind)
       fatal(__FUNCTION__, "number of lines in --ind_names file is not --n_ind!");
     if (!P.ibd_bed && !P.sample_paths && !P.indF_se && !P.ibd_summary && !P.ibd_sharing && !P.ibd_support &&
-        !P.ibd_bounds && !P.geno_summary && !P.ibd_expect)
-      warn(__FUNCTION__, "--ind_names is only used by --ibd_bed, --sample_paths, --indF_se, --ibd_summary, --ibd_sharing, --ibd_support, --ibd_bounds, --geno_summary and --ibd_expect");
+        !P.ibd_bounds && !P.geno_summary && !P.ibd_expect && !P.ibd_moments)
+      warn(__FUNCTION__, "--ind_names is only used by --ibd_bed, --sample_paths, --indF_se, --ibd_summary, --ibd_sharing, --ibd_support, --ibd_bounds, --geno_summary, --ibd_expect and --ibd_moments");
   }
   P.prefix = P.out_prefix;
 }
@@ -2253,6 +2328,7 @@ void finish_run(Params& P, Cohort& C) {
   if (P.freq_info) write_freq_info(P, C);
   if (P.geno_smooth || P.geno_summary) write_geno_smooth(P, C);
   if (P.ibd_expect) write_ibd_expect(P, C);
+  if (P.ibd_moments) write_ibd_moments(P, C);
   if (P.verbose >= 2)  // (not a line of the reference's)
     fprintf(P.out, "> decoded in %.2f s, output files written in %.2f s\n", t1 - t0, omp_get_wtime() - t1);
 }
@@ -2374,6 +2450,7 @@ int main(int argc, char** argv) {
         runs[r].geno_smooth = P.geno_smooth && r == best;
         runs[r].geno_summary = P.geno_summary && r == best;
         runs[r].ibd_expect = P.ibd_expect && r == best;
+        runs[r].ibd_moments = P.ibd_moments && r == best;
         finish_run(runs[r], cs[r]);
       }
       fclose(runs[r].out);
@@ -2403,6 +2480,7 @@ int main(int argc, char** argv) {
         exts.push_back(".ibd.expect");
         exts.push_back(".ibd.breaks");
       }
+      if (P.ibd_moments) exts.push_back(".ibd.moments");
       for (unsigned k = 1; P.sample_paths && k <= P.sample_keep; k++) {
         char tag[32];
         snprintf(tag, sizeof tag, ".sample_%02u.ibd", k);

@@ -167,6 +167,9 @@ def load_library():
         "nghmm_ibd_expect": (i32, [vp, i32, u64, C.POINTER(u64), C.POINTER(u64), vp, vp]),
         "nghmm_chain_ibd_expect": (i32, [C.POINTER(vp), i32, i32, u64, C.POINTER(u64), C.POINTER(u64),
                                          vp, vp]),
+        "nghmm_ibd_moments": (i32, [vp, i32, u64, C.POINTER(u64), C.POINTER(u64), vp]),
+        "nghmm_chain_ibd_moments": (i32, [C.POINTER(vp), i32, i32, u64, C.POINTER(u64), C.POINTER(u64),
+                                          vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -212,6 +215,7 @@ EXPORTED_SYMBOLS = [
     "nghmm_ibd_summary", "nghmm_chain_ibd_summary",
     "nghmm_ibd_sharing", "nghmm_chain_ibd_sharing",
     "nghmm_ibd_expect", "nghmm_chain_ibd_expect",
+    "nghmm_ibd_moments", "nghmm_chain_ibd_moments",
 ]
 
 OBJECTIVE_FN = C.CFUNCTYPE(C.c_double, C.c_uint32, C.c_double, C.c_double, C.c_void_p)
@@ -661,6 +665,66 @@ def expect_tract_length(region_stats):
     np.divide(region_stats["ibd"], st, out=sites, where=st != 0)
     np.divide(region_stats["ibd_mb"], st, out=mb, where=st != 0)
     return sites, mb
+
+
+MOMENTS_MB = 1         # nghmm_ibd_moments: A = IBD Mb instead of IBD sites
+
+
+class MomentRegion(C.Structure):     # nghmm_moment_region (include/nghmm.h)
+    _fields_ = [(n, C.c_double) for n in ("mean_a", "mean_t", "var_a", "cov_at", "var_t")]
+
+
+MOMENT_REGION_DTYPE = np.dtype([(n, np.float64) for n, _ in MomentRegion._fields_])
+assert MOMENT_REGION_DTYPE.itemsize == C.sizeof(MomentRegion) == 40
+
+
+def _ibd_moments(call, check, n_ind, n_sites, regions, length):
+    u64p = C.POINTER(C.c_uint64)
+    if length not in ("sites", "mb"):
+        raise NgsFHMMError(-10, "ibd_moments: length is 'sites' or 'mb'")
+    if regions is None:
+        reg = np.array([[0, n_sites]], dtype=np.uint64)
+    else:
+        reg = np.asarray(regions)
+        if reg.size == 0:
+            reg = reg.reshape(0, 2)
+        if reg.ndim != 2 or reg.shape[1] != 2 or not np.issubdtype(reg.dtype, np.integer) or \
+                (reg < 0).any():
+            raise NgsFHMMError(-10, "ibd_moments: regions is an [R][2] array of site indices "
+                                    "(begin, end)")
+        reg = reg.astype(np.uint64)
+    R = len(reg)
+    begin, end = np.ascontiguousarray(reg[:, 0]), np.ascontiguousarray(reg[:, 1])
+    stats = np.zeros((n_ind, R), dtype=MOMENT_REGION_DTYPE)
+    check(call(MOMENTS_MB if length == "mb" else 0, R,
+               begin.ctypes.data_as(u64p) if R else None, end.ctypes.data_as(u64p) if R else None,
+               C.c_void_p(stats.ctypes.data) if R else None))
+    return stats
+
+
+def moment_sd(stats):
+    """What ibd_moments' records say about uncertainty, as a dict of arrays of stats' shape:
+    sd_a, sd_t (posterior standard deviations), corr (NaN where a variance is 0), tract_length =
+    mean_a / mean_t and tract_length_sd, its delta-method posterior sd
+    sqrt(var_a - 2 R cov_at + R^2 var_t) / mean_t with R = tract_length (both NaN where mean_t is
+    0)."""
+    va = np.asarray(stats["var_a"], dtype=np.float64)
+    vt = np.asarray(stats["var_t"], dtype=np.float64)
+    cov = np.asarray(stats["cov_at"], dtype=np.float64)
+    ma = np.asarray(stats["mean_a"], dtype=np.float64)
+    mt = np.asarray(stats["mean_t"], dtype=np.float64)
+    sd_a, sd_t = np.sqrt(va), np.sqrt(vt)
+    corr = np.full(va.shape, np.nan)
+    ok = (va > 0) & (vt > 0)
+    np.divide(cov, sd_a * sd_t, out=corr, where=ok)
+    ratio = np.full(va.shape, np.nan)
+    np.divide(ma, mt, out=ratio, where=mt != 0)
+    with np.errstate(invalid="ignore"):
+        q = np.maximum(va - 2 * ratio * cov + ratio * ratio * vt, 0.0)
+        length_sd = np.full(va.shape, np.nan)
+        np.divide(np.sqrt(q), np.abs(mt), out=length_sd, where=mt != 0)
+    return {"sd_a": sd_a, "sd_t": sd_t, "corr": corr, "tract_length": ratio,
+            "tract_length_sd": length_sd}
 
 
 SHARING_VITERBI = 1    # nghmm_ibd_sharing sources, a bit mask (include/nghmm.h)
@@ -1205,6 +1269,15 @@ class NgsFHMM:
         return _ibd_expect(lambda *a: self.lib.nghmm_ibd_expect(self._h, *a), self._check,
                            self.n_ind, self.n_sites, regions, sites, viterbi)
 
+    def ibd_moments(self, regions=None, length="sites"):
+        """Exact posterior means and covariances of (IBD length, number of tracts) per individual
+        and region (nghmm_ibd_moments): [I][R] of MOMENT_REGION_DTYPE (mean_a, mean_t, var_a,
+        cov_at, var_t; regions as ibd_summary takes them, None = one region over all sites).
+        length: "sites" (A = IBD sites) or "mb" (A = IBD Mb).  Conditional on indF, alpha and the
+        frequencies; moment_sd turns the records into standard deviations."""
+        return _ibd_moments(lambda *a: self.lib.nghmm_ibd_moments(self._h, *a), self._check,
+                            self.n_ind, self.n_sites, regions, length)
+
     def ibd_sharing(self, what=("viterbi", "posterior"), threshold=0.5, site_begin=0, site_end=None):
         """Pairwise IBD sharing over the sites [site_begin, site_end) (default: all), reduced on
         the matrix cores (nghmm_ibd_sharing).  what: "viterbi" (vit_both, from the last decode),
@@ -1390,6 +1463,14 @@ class Chain:
         return _ibd_expect(
             lambda *a: self.lib.nghmm_chain_ibd_expect(self._arr, len(self.handles), *a),
             self.handles[0]._check, self.n_ind, self.n_sites, regions, sites, viterbi)
+
+    def ibd_moments(self, regions=None, length="sites"):
+        """NgsFHMM.ibd_moments over the chain (nghmm_chain_ibd_moments): global site indices, a
+        region across a shard boundary is one region; within rounding of a single handle's values."""
+        self._members_open()
+        return _ibd_moments(
+            lambda *a: self.lib.nghmm_chain_ibd_moments(self._arr, len(self.handles), *a),
+            self.handles[0]._check, self.n_ind, self.n_sites, regions, length)
 
     def ibd_sharing(self, what=("viterbi", "posterior"), threshold=0.5, site_begin=0, site_end=None):
         """NgsFHMM.ibd_sharing over the chain (nghmm_chain_ibd_sharing): global site indices, the
