@@ -983,6 +983,95 @@ int nghmm_chain_ibd_moments(nghmm_t** hs, int n_handles, int what, uint64_t n_re
                             const uint64_t* region_begin, const uint64_t* region_end,
                             nghmm_moment_region* regions);
 
+/* ---- expected IBD above a minimum tract length ----
+ * Per individual, region and threshold L_k the expected number of IBD tracts of length >= L_k
+ * that begin in the region and the expected total length of those tracts, exactly, at the
+ * handle's CURRENT parameters and emissions.  Tracts and lengths are nghmm_path_stats's: runs of
+ * z = 1 cut at chromosome starts; in Mb the distance from a tract's first site to its last, so a
+ * one-site tract is 0 Mb.  Notation of nghmm_ibd_expect (m_s, xi_s, r_s, pi_s, start_s,
+ * chromosome starts, d_s).  Given the data the path is a Markov chain, so with
+ *   sigma_s = start_s (xi_s(0, 1), or pi_s(1) at a chromosome start)
+ *   rho_s   = r_s(1, 1) = m_s(1, 1) / (m_s(1, 0) + m_s(1, 1)), 0 for 0/0 and at a chromosome
+ *             start; the step into s is BLOCKED iff rho_s == 0
+ *   W(a, b) = prod_{s = a+1..b} rho_s, W(a, a) = 1
+ * a tract begins at a and covers a..b with probability sigma_a W(a, b), and the run goes on beyond
+ * b for M_b further sites, D_b further Mb in expectation:
+ *   M_s = rho_{s+1} (1 + M_{s+1}),  D_s = rho_{s+1} (d_{s+1} + D_{s+1}),  0 at the last site; a
+ *   blocked step gives 0, never inf * 0.
+ * K thresholds, 1 <= K <= 8, strictly increasing.  In sites (default) len(a, b) = b - a + 1,
+ * rem_b = M_b and the thresholds are integers >= 1; with NGHMM_BYLENGTH_MB len(a, b) = cum_b -
+ * cum_a, rem_b = D_b and the thresholds are finite and >= 0, where cum_s = 0 at a chromosome start
+ * and cum_{s-1} + d_s elsewhere (formed on the host in double, in site order).  b_k(a) is the
+ * smallest b >= a in a's chromosome with len(a, b) >= L_k; if there is none, (a, k) contributes
+ * nothing.  Then
+ *   tracts_k(a) = sigma_a W(a, b_k(a)),  length_k(a) = tracts_k(a) (len(a, b_k(a)) + rem_{b_k(a)})
+ * and the record [i][region][k] is the sum of the terms over the start sites a of the region
+ * (nghmm_ibd_summary's regions): a tract belongs to the region in which it BEGINS, with its whole
+ * length, even past the region's end; regions that partition the data add up to the whole.  Over
+ * all sites tracts = E[number of tracts of length >= L_k | y] and length = E[their total length |
+ * y].  With L = 1 site tracts is nghmm_ibd_expect's starts and, over whole chromosomes, length its
+ * ibd; with L = 0 Mb length is its ibd_mb.  Both fields are non-increasing in k, length >= L_k
+ * tracts, and differences of successive thresholds are the length classes [L_k, L_{k+1}).  A state
+ * the data exclude gives exact zeros; nothing is NaN or inf.
+ *
+ * NGHMM_ERR_ARG with a message: n_lengths of 0 or above 8; thresholds that are not strictly
+ * increasing, not finite, negative, or (in sites) not integers >= 1; an unknown bit in what; a
+ * handle without data; NULL arguments and region faults as nghmm_ibd_expect reports them.
+ *
+ * Orders (no float atomics; the same arguments give the same bits on every call, and a region's
+ * record does not depend on which other regions are asked for).  W(a, b) is formed as
+ * n_b == n_a ? exp(Q_b - Q_a) : 0 from the prefix Q_s = sum of ln rho, which restarts from 0 at
+ * every blocked step (a chromosome start is one), and the count n_s of blocked steps at or in
+ * front of s; ln rho comes from the small side as in nghmm_ibd_expect.  Fast mode, in the layout
+ * of nghmm_fast_layout (a lane-chunk is T consecutive sites): within a lane-chunk Q is added in
+ * site order from the value that enters it; that value is the sum of the lane-chunks in front of
+ * it back to the last blocked step, where a lane-chunk's own sum is added from its last site to
+ * its first, the 64 lane-chunks of a wave in a Hillis-Steele tree (steps 1, 2, .., 32) and the
+ * waves in site order.  M and D: per lane-chunk the affine map x -> A x + B of its sites composed
+ * from its last site to its first, the maps of a wave composed in the same tree right to left, the
+ * waves right to left; inside a lane-chunk the recursion itself from the chunk-end value.  All
+ * coefficients lie in [0, 1] (B in units of sites or Mb): nothing cancels.  A region's sum: pieces
+ * at the lane-chunk edges, each added from its last site to its first, the pieces in site order,
+ * as nghmm_ibd_expect.  Exact mode: one lane per individual in log space, Q in site order, a
+ * region's terms added to 0 from its last site to its first.
+ *
+ * Accuracy of W: Q_b - Q_a is a difference of prefix sums, so the exponent carries an absolute
+ * error of about 2^-53 max|Q| between two restarts.  |Q| grows only through stretches that are
+ * neither blocked nor confidently IBD; at 10^6 sites a long confidently non-IBD stretch can push
+ * it to ~10^6, a relative error of ~1e-10 in a term (and such terms are themselves ~ exp(-|Q|)).
+ * nghmm_debug_bylength_qmax (nghmm_debug.h) reports the largest |Q| of the last call.
+ *
+ * Self-contained and read-only exactly like nghmm_ibd_expect: it refreshes stale emissions itself
+ * and leaves parameters, posteriors, the Viterbi path, checkpoints and an M-step planned in advance
+ * untouched; an EM iteration after the call gives the bits it would have given without it.  Device
+ * scratch, kept by the handle and allocated on first use (NGHMM_ERR_NOMEM when it cannot be had):
+ * 36 bytes per cell (sigma, Q, n, M, D) in a buffer of its own; 64 bytes per (individual,
+ * lane-chunk); 4 n_lengths + 8 bytes per site for b_k and cum; 16 n_lengths per (individual,
+ * piece) and per (individual, region).   */
+enum { NGHMM_BYLENGTH_MB = 1 };
+typedef struct nghmm_bylength_stat {  /* 16 bytes; one per (individual, region, threshold) */
+  double tracts;  /* expected number of tracts of length >= L_k that begin in the region */
+  double length;  /* expected total length of those tracts, in sites or Mb */
+} nghmm_bylength_stat;
+#ifdef __cplusplus
+static_assert(sizeof(nghmm_bylength_stat) == 16, "record size");
+#endif
+/* stats [I][n_regions][n_lengths] (host) */
+int nghmm_ibd_by_length(nghmm_t* h, int what, uint32_t n_lengths, const double* min_length,
+                        uint64_t n_regions, const uint64_t* region_begin, const uint64_t* region_end,
+                        nghmm_bylength_stat* stats);
+/* The same over a chain of site shards (nghmm_chain_setup, else NGHMM_ERR_ARG): global site
+ * indices.  M and D travel right to left across the cuts; a shard receives from its right
+ * neighbour Q, n and rem of as many of the neighbour's first sites as its own windows reach (Q
+ * and n start afresh in every shard, and a window across the cut is the product of its two
+ * parts).  A threshold whose window from a shard's last sites reaches past the NEXT shard is
+ * NGHMM_ERR_ARG with a message.  A region across a cut is one region, its parts added on the host
+ * in rank order.  The results are within rounding of a single handle's, not its bytes.  (Chains
+ * of more than one handle are fast mode only.) */
+int nghmm_chain_ibd_by_length(nghmm_t** hs, int n_handles, int what, uint32_t n_lengths,
+                              const double* min_length, uint64_t n_regions, const uint64_t* region_begin,
+                              const uint64_t* region_end, nghmm_bylength_stat* stats);
+
 /* ---- pairwise IBD sharing between individuals ----
  * How much IBD two individuals share over the sites [site_begin, site_end): three host matrices
  * [I][I], full and symmetric, reduced on the matrix cores from the decoded path and the

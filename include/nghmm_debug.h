@@ -94,6 +94,11 @@ typedef struct {
 int nghmm_debug_mode_counts(nghmm_t* h, nghmm_mode_count* out, uint32_t cap, uint32_t* n, int reset);
 int nghmm_debug_estmaf_counts(nghmm_t* h, uint64_t out[5], int reset);
 
+/* The largest |Q| (the prefix sum of ln rho between two restarts) that the handle's last
+ * nghmm_ibd_by_length / nghmm_chain_ibd_by_length met on this handle: times 2^-53 it bounds the
+ * absolute error in the exponent of W (include/nghmm.h).  0 before the first call. */
+int nghmm_debug_bylength_qmax(nghmm_t* h, double* qmax);
+
 #ifdef __cplusplus
 }
 #endif

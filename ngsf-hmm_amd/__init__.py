@@ -24,7 +24,8 @@ from .hmm import (NgsFHMM, NgsFHMMError, Group, Chain, MODE_EXACT, MODE_FAST, GE
                   TRACT_BOUND_DTYPE, NO_ANCHOR, FREQ_STAT_DTYPE, freq_std_errors,
                   GENO_SITE_STAT_DTYPE, GENO_REGION_STAT_DTYPE, geno_em_freq, het_outside_ibd,
                   EXPECT_VITERBI, EXPECT_REGION_DTYPE, EXPECT_SITE_DTYPE, expect_tract_length,
-                  MOMENTS_MB, MOMENT_REGION_DTYPE, moment_sd)
+                  MOMENTS_MB, MOMENT_REGION_DTYPE, moment_sd,
+                  BYLENGTH_MB, BYLENGTH_DTYPE, by_length_classes)
 from . import simulate
 
 __all__ = ["NgsFHMM", "NgsFHMMError", "Group", "Chain", "MODE_EXACT", "MODE_FAST", "GENO_PACKED", "LD_INTENDED", "EPROB_LD", "library_path",
@@ -37,4 +38,4 @@ __all__ = ["NgsFHMM", "NgsFHMMError", "Group", "Chain", "MODE_EXACT", "MODE_FAST
            "FREQ_STAT_DTYPE", "freq_std_errors", "GENO_SITE_STAT_DTYPE", "GENO_REGION_STAT_DTYPE",
            "geno_em_freq", "het_outside_ibd", "EXPECT_VITERBI", "EXPECT_REGION_DTYPE",
            "EXPECT_SITE_DTYPE", "expect_tract_length", "MOMENTS_MB", "MOMENT_REGION_DTYPE",
-           "moment_sd"]
+           "moment_sd", "BYLENGTH_MB", "BYLENGTH_DTYPE", "by_length_classes"]

@@ -1,6 +1,6 @@
 // capi_internal.hpp -- what the translation units of the C ABI share: the handle, error plumbing,
 // and the helpers every entry point uses.  nghmm_capi.hip (handle life cycle, single-handle EM),
-// capi_load.hip (loaders), capi_output.hip (read-back and output formatting), capi_tracts.hip, capi_sample.hip, capi_info.hip, capi_summary.hip, capi_sharing.hip, capi_support.hip, capi_bounds.hip, capi_cavity.hip, capi_freqinfo.hip, capi_genosmooth.hip, capi_expect.hip, capi_moments.hip and
+// capi_load.hip (loaders), capi_output.hip (read-back and output formatting), capi_tracts.hip, capi_sample.hip, capi_info.hip, capi_summary.hip, capi_sharing.hip, capi_support.hip, capi_bounds.hip, capi_cavity.hip, capi_freqinfo.hip, capi_genosmooth.hip, capi_expect.hip, capi_moments.hip, capi_bylength.hip and
 // capi_multi.hip (individual shards, site shards, groups and chains of handles) implement include/nghmm.h.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -129,6 +129,12 @@ struct nghmm_handle {
   // posterior moments of IBD share and tract count (capi_moments.hip): the piece and segment
   // tables, the centred jets of the pieces and of the segments, the backward vectors, the records
   DevScratch<uint8_t> d_mom;
+  // expected IBD above a minimum tract length (capi_bylength.hip): the regions, their pieces and
+  // records, the lane-chunk maps and scans, the b_k and cum tables, the boundary vectors and the
+  // halo; and the per-cell planes (36 bytes per cell) in an owner of their own
+  DevScratch<uint8_t> d_byl;
+  DevScratch<uint8_t> d_byl_cell;
+  double byl_qmax = 0;   // the largest |Q| of the last call (nghmm_debug_bylength_qmax)
   DevBuf<double> d_freq_new, d_hap;  // --freq_est 2 as intended: [S], [S][4]
 
   // multi-GPU shard

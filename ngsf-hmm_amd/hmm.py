@@ -170,6 +170,10 @@ def load_library():
         "nghmm_ibd_moments": (i32, [vp, i32, u64, C.POINTER(u64), C.POINTER(u64), vp]),
         "nghmm_chain_ibd_moments": (i32, [C.POINTER(vp), i32, i32, u64, C.POINTER(u64), C.POINTER(u64),
                                           vp]),
+        "nghmm_ibd_by_length": (i32, [vp, i32, u32, dp, u64, C.POINTER(u64), C.POINTER(u64), vp]),
+        "nghmm_chain_ibd_by_length": (i32, [C.POINTER(vp), i32, i32, u32, dp, u64, C.POINTER(u64),
+                                            C.POINTER(u64), vp]),
+        "nghmm_debug_bylength_qmax": (i32, [vp, dp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -216,6 +220,7 @@ EXPORTED_SYMBOLS = [
     "nghmm_ibd_sharing", "nghmm_chain_ibd_sharing",
     "nghmm_ibd_expect", "nghmm_chain_ibd_expect",
     "nghmm_ibd_moments", "nghmm_chain_ibd_moments",
+    "nghmm_ibd_by_length", "nghmm_chain_ibd_by_length", "nghmm_debug_bylength_qmax",
 ]
 
 OBJECTIVE_FN = C.CFUNCTYPE(C.c_double, C.c_uint32, C.c_double, C.c_double, C.c_void_p)
@@ -725,6 +730,58 @@ def moment_sd(stats):
         np.divide(np.sqrt(q), np.abs(mt), out=length_sd, where=mt != 0)
     return {"sd_a": sd_a, "sd_t": sd_t, "corr": corr, "tract_length": ratio,
             "tract_length_sd": length_sd}
+
+
+BYLENGTH_MB = 1        # nghmm_ibd_by_length: thresholds and lengths in Mb instead of sites
+
+
+class ByLengthStat(C.Structure):     # nghmm_bylength_stat (include/nghmm.h)
+    _fields_ = [(n, C.c_double) for n in ("tracts", "length")]
+
+
+BYLENGTH_DTYPE = np.dtype([(n, np.float64) for n, _ in ByLengthStat._fields_])
+assert BYLENGTH_DTYPE.itemsize == C.sizeof(ByLengthStat) == 16
+
+
+def _ibd_by_length(call, check, n_ind, n_sites, min_len, unit, regions):
+    u64p = C.POINTER(C.c_uint64)
+    if unit not in ("sites", "mb"):
+        raise NgsFHMMError(-10, "ibd_by_length: unit is 'sites' or 'mb'")
+    L = np.ascontiguousarray(np.atleast_1d(np.asarray(min_len, dtype=np.float64)))
+    if L.ndim != 1:
+        raise NgsFHMMError(-10, "ibd_by_length: min_len is a number or a list of numbers")
+    if regions is None:
+        reg = np.array([[0, n_sites]], dtype=np.uint64)
+    else:
+        reg = np.asarray(regions)
+        if reg.size == 0:
+            reg = reg.reshape(0, 2)
+        if reg.ndim != 2 or reg.shape[1] != 2 or not np.issubdtype(reg.dtype, np.integer) or \
+                (reg < 0).any():
+            raise NgsFHMMError(-10, "ibd_by_length: regions is an [R][2] array of site indices "
+                                    "(begin, end)")
+        reg = reg.astype(np.uint64)
+    R, K = len(reg), len(L)
+    begin, end = np.ascontiguousarray(reg[:, 0]), np.ascontiguousarray(reg[:, 1])
+    stats = np.zeros((n_ind, R, K), dtype=BYLENGTH_DTYPE)
+    check(call(BYLENGTH_MB if unit == "mb" else 0, K, _dp(L) if K else None, R,
+               begin.ctypes.data_as(u64p) if R else None, end.ctypes.data_as(u64p) if R else None,
+               C.c_void_p(stats.ctypes.data) if R and K else None))
+    return stats
+
+
+def by_length_classes(stats):
+    """ibd_by_length's records [..][K] as length classes: a dict of float arrays [..][K], class k
+    being [L_k, L_{k+1}) and the last one open: tracts and length as differences of successive
+    thresholds, mean_length = length / tracts (NaN where tracts is 0)."""
+    tr = np.asarray(stats["tracts"], dtype=np.float64)
+    ln = np.asarray(stats["length"], dtype=np.float64)
+    ct, cl = tr.copy(), ln.copy()
+    ct[..., :-1] -= tr[..., 1:]
+    cl[..., :-1] -= ln[..., 1:]
+    mean = np.full(ct.shape, np.nan)
+    np.divide(cl, ct, out=mean, where=ct != 0)
+    return {"tracts": ct, "length": cl, "mean_length": mean}
 
 
 SHARING_VITERBI = 1    # nghmm_ibd_sharing sources, a bit mask (include/nghmm.h)
@@ -1278,6 +1335,23 @@ class NgsFHMM:
         return _ibd_moments(lambda *a: self.lib.nghmm_ibd_moments(self._h, *a), self._check,
                             self.n_ind, self.n_sites, regions, length)
 
+    def ibd_by_length(self, min_len, unit="sites", regions=None):
+        """Expected IBD above a minimum tract length, exactly (nghmm_ibd_by_length): [I][R][K] of
+        BYLENGTH_DTYPE -- tracts, the expected number of IBD tracts of at least min_len[k] that
+        begin in the region, and length, their expected total length.  min_len: 1 to 8 strictly
+        increasing thresholds in sites (whole numbers >= 1) or, with unit="mb", in Mb (>= 0; a
+        tract's Mb run from its first site to its last); regions as ibd_summary takes them, None
+        = one region over all sites.  by_length_classes turns the records into length classes."""
+        return _ibd_by_length(lambda *a: self.lib.nghmm_ibd_by_length(self._h, *a), self._check,
+                              self.n_ind, self.n_sites, min_len, unit, regions)
+
+    def by_length_qmax(self):
+        """The largest |Q| the last ibd_by_length met (nghmm_debug_bylength_qmax): times 2^-53 the
+        absolute error in the exponent of a window's probability."""
+        q = C.c_double(0.0)
+        self._check(self.lib.nghmm_debug_bylength_qmax(self._h, C.byref(q)))
+        return q.value
+
     def ibd_sharing(self, what=("viterbi", "posterior"), threshold=0.5, site_begin=0, site_end=None):
         """Pairwise IBD sharing over the sites [site_begin, site_end) (default: all), reduced on
         the matrix cores (nghmm_ibd_sharing).  what: "viterbi" (vit_both, from the last decode),
@@ -1471,6 +1545,15 @@ class Chain:
         return _ibd_moments(
             lambda *a: self.lib.nghmm_chain_ibd_moments(self._arr, len(self.handles), *a),
             self.handles[0]._check, self.n_ind, self.n_sites, regions, length)
+
+    def ibd_by_length(self, min_len, unit="sites", regions=None):
+        """NgsFHMM.ibd_by_length over the chain (nghmm_chain_ibd_by_length): global site indices, a
+        region across a shard boundary is one region, a window may reach into the next shard but
+        not past it; within rounding of a single handle's values."""
+        self._members_open()
+        return _ibd_by_length(
+            lambda *a: self.lib.nghmm_chain_ibd_by_length(self._arr, len(self.handles), *a),
+            self.handles[0]._check, self.n_ind, self.n_sites, min_len, unit, regions)
 
     def ibd_sharing(self, what=("viterbi", "posterior"), threshold=0.5, site_begin=0, site_end=None):
         """NgsFHMM.ibd_sharing over the chain (nghmm_chain_ibd_sharing): global site indices, the
