@@ -16,10 +16,8 @@
 #include <algorithm>
 #include <limits>
 
-#include "capi_internal.hpp"
+#include "capi_chain.hpp"
 #include "kernels_bounds.hpp"
-#include "kernels_sample.hpp"
-#include "kernels_support.hpp"
 
 static_assert(sizeof(nghmm_tract_bound) == 48, "nghmm_tract_bound is 48 bytes");
 
@@ -84,20 +82,19 @@ int run_pass(nghmm_t** hs, int n, bool fast, uint64_t I, std::vector<Shard>& sh,
     x.out.assign(n_out * rec_size, 0);
     if (m == 0) continue;
     if ((rc = use_device(h))) return rc;
-    const uint64_t b_rec = align256(m * sizeof(BoundRange)), b_ioff = align256((I + 1) * sizeof(uint64_t)),
-                   b_off = align256(x.n_pieces * sizeof(BoundOff)), b_out = align256(x.n_pieces * rec_size),
-                   b_fin = pass == 2 ? align256(m * rec_size) : 0;
-    if ((rc = h->d_bnd.reserve(b_rec + b_ioff + b_off + b_out + b_fin))) return rc;
-    uint8_t* p = h->d_bnd.p;
-    BoundRange* d_rec = reinterpret_cast<BoundRange*>(p);
-    p += b_rec;
-    uint64_t* d_ioff = reinterpret_cast<uint64_t*>(p);
-    p += b_ioff;
-    BoundOff* d_off = reinterpret_cast<BoundOff*>(p);
-    p += b_off;
-    void* d_out = p;
-    p += b_out;
-    void* d_fin = (pass == 2 && fast) ? p : d_out;   // (exact mode: a range is its one piece)
+    BoundRange* d_rec;
+    uint64_t* d_ioff;
+    BoundOff* d_off;
+    uint8_t *d_pieces, *d_ranges;   // the pass's records per piece; locate: per range
+    Carver cv;
+    cv.add(&d_rec, m);
+    cv.add(&d_ioff, I + 1);
+    cv.add(&d_off, x.n_pieces);
+    cv.add(&d_pieces, x.n_pieces * rec_size);
+    cv.add(&d_ranges, pass == 2 ? m * rec_size : 0);
+    if ((rc = cv.reserve(h->d_bnd))) return rc;
+    void* d_out = d_pieces;
+    void* d_fin = (pass == 2 && fast) ? d_ranges : d_out;   // (exact mode: a range is its one piece)
     HIP_TRY(hipMemcpyAsync(d_rec, x.rec.data(), m * sizeof(BoundRange), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(hipMemcpyAsync(d_ioff, x.ioff.data(), (I + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, h->stream));
     if (pass == 2)
@@ -110,11 +107,7 @@ int run_pass(nghmm_t** hs, int n, bool fast, uint64_t I, std::vector<Shard>& sh,
                                         static_cast<BoundSum*>(d_out))
                       : bounds_fast_locate(h->fast, h->stream, h->d_indF, h->d_alpha, d_ioff, d_rec, d_off, lv,
                                            static_cast<BoundFail*>(d_out), m, static_cast<BoundFail*>(d_fin));
-      if (!ok) {
-        set_error("%s: the fast layout (T = %llu sites per lane) is not one the walk knows, or a kernel "
-                  "launch failed", who, (unsigned long long)h->fast.T);
-        return NGHMM_ERR_HIP;
-      }
+      if (!ok) return fast_layout_error(h, who);
     } else {
       if ((rc = clear_flags(h))) return rc;
       launch_bounds_exact(pass, h->stream, h->d_eprob, h->d_pos, h->d_fw, h->S, I, h->d_indF, h->d_alpha, d_ioff,
@@ -143,11 +136,8 @@ void for_pieces(nghmm_t** hs, int n, bool fast, const std::vector<Shard>& sh, si
 int bounds_impl(nghmm_t** hs, int n, const nghmm_tract* tracts, uint64_t n_rec, const uint64_t* anchor,
                 const double* levels, uint32_t n_levels, nghmm_tract_bound* out, uint64_t* start,
                 uint64_t* end, const char* who) {
-  for (int r = 0; r < n; ++r)
-    if (!hs[r] || !hs[r]->loaded) {
-      set_error("%s: the handle holds no data", who);
-      return NGHMM_ERR_ARG;
-    }
+  int rc;
+  if ((rc = chain_check_loaded(hs, n, who))) return rc;
   if (n_rec == 0) return NGHMM_OK;
   if (n_levels < 1 || n_levels > BOUNDS_MAX_LEVELS) {
     set_error("%s: n_levels = %u: between 1 and %u levels", who, n_levels, BOUNDS_MAX_LEVELS);
@@ -174,10 +164,7 @@ int bounds_impl(nghmm_t** hs, int n, const nghmm_tract* tracts, uint64_t n_rec, 
     lv.ln[m] = std::log(levels[m]);
   }
   const bool fast = hs[0]->mode == NGHMM_MODE_FAST;
-  if (n > 1 && !fast) {
-    set_error("%s: site shards are a fast-mode layout", who);
-    return NGHMM_ERR_ARG;
-  }
+  if ((rc = chain_check_fast(hs, n, who))) return rc;
   const uint64_t I = hs[0]->I;
   std::vector<Shard> sh(n);
   uint64_t S_tot = 0;
@@ -185,71 +172,35 @@ int bounds_impl(nghmm_t** hs, int n, const nghmm_tract* tracts, uint64_t n_rec, 
     sh[r].base = S_tot;
     S_tot += hs[r]->S;
   }
-  // the records: inside the data, ordered by (ind, first_site), disjoint within an individual
-  // (nghmm_tract_support's checks and messages); the anchors inside their cores
+  // the records, one by one: nghmm_tract_support's checks, then the anchor inside its core
   for (uint64_t k = 0; k < n_rec; ++k) {
+    if ((rc = check_tract_record(tracts, k, I, S_tot, who))) return rc;
     const nghmm_tract& t = tracts[k];
-    const unsigned long long kk = k, a = t.first_site, len = t.n_sites;
-    if (t.n_sites == 0) {
-      set_error("%s: record %llu has n_sites = 0", who, kk);
-      return NGHMM_ERR_ARG;
-    }
-    if (t.ind >= I) {
-      set_error("%s: record %llu has ind = %u, of %llu individuals", who, kk, t.ind, (unsigned long long)I);
-      return NGHMM_ERR_ARG;
-    }
-    if (t.first_site >= S_tot || t.n_sites > S_tot - t.first_site) {
-      set_error("%s: record %llu, sites [%llu, %llu + %llu), is outside the data's %llu sites", who, kk, a, a,
-                len, (unsigned long long)S_tot);
-      return NGHMM_ERR_ARG;
-    }
-    if (k > 0) {
-      const nghmm_tract& p = tracts[k - 1];
-      if (t.ind < p.ind || (t.ind == p.ind && t.first_site < p.first_site + p.n_sites)) {
-        set_error("%s: record %llu (ind %u, first_site %llu) is out of order or overlaps record %llu: the "
-                  "records are ordered by (ind, first_site) and disjoint within an individual", who, kk,
-                  t.ind, a, kk - 1);
-        return NGHMM_ERR_ARG;
-      }
-    }
     if (anchor && anchor[k] != UINT64_MAX && (anchor[k] < t.first_site || anchor[k] - t.first_site >= t.n_sites)) {
-      set_error("%s: record %llu: the anchor %llu is outside its core, sites [%llu, %llu + %llu)", who, kk,
-                (unsigned long long)anchor[k], a, a, len);
+      const unsigned long long a = t.first_site, len = t.n_sites;
+      set_error("%s: record %llu: the anchor %llu is outside its core, sites [%llu, %llu + %llu)", who,
+                (unsigned long long)k, (unsigned long long)anchor[k], a, a, len);
       return NGHMM_ERR_ARG;
     }
   }
-  int rc;
-  // the boundary vectors of every shard: the forward half first shard to last ...
+  // the boundary vectors of every shard: the forward half first shard to last, the backward half
+  // last shard to first.  (The two vectors lie at the front of d_bnd, which run_pass carves anew:
+  // by then fast.bound holds what they carried.  A backward half that cannot launch returns its
+  // code without a message of this call's.)
   if (fast) {
-    std::vector<double> vec((size_t)I * 2);
-    const uint64_t b_vec = align256(I * 2 * sizeof(double));
+    ChainRelay relay(hs, n, true);
     for (int r = 0; r < n; ++r) {
       nghmm_t* h = hs[r];
       if ((rc = use_device(h))) return rc;
-      if ((rc = h->d_bnd.reserve(2 * b_vec))) return rc;
-      double* d_vin = reinterpret_cast<double*>(h->d_bnd.p);
-      double* d_vout = reinterpret_cast<double*>(h->d_bnd.p + b_vec);
-      if ((rc = clear_flags(h))) return rc;
-      if ((rc = ensure_emissions(h))) return rc;
-      if (r > 0) HIP_TRY(hipMemcpyAsync(d_vin, vec.data(), I * 2 * sizeof(double), hipMemcpyHostToDevice, h->stream));
-      if (!sample_fast_forward(h->fast, h->stream, h->d_indF, h->d_alpha, r ? d_vin : nullptr, d_vout))
-        return NGHMM_ERR_HIP;
-      if (r + 1 < n)
-        HIP_TRY(hipMemcpyAsync(vec.data(), d_vout, I * 2 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-      HIP_TRY(hipGetLastError());
-      if ((rc = check_flags(h))) return rc;   // (waits for the stream)
+      Carver cv;
+      relay.add(cv, r);
+      if ((rc = cv.reserve(h->d_bnd))) return rc;
+      if ((rc = relay.forward(r))) return rc;
     }
-    // ... the backward half last shard to first
     for (int r = n - 1; r >= 0; --r) {
       nghmm_t* h = hs[r];
-      const bool last = r == n - 1;
       if ((rc = use_device(h))) return rc;
-      double* d_win = reinterpret_cast<double*>(h->d_bnd.p);
-      double* d_wout = reinterpret_cast<double*>(h->d_bnd.p + b_vec);
-      if (!last) HIP_TRY(hipMemcpyAsync(d_win, vec.data(), I * 2 * sizeof(double), hipMemcpyHostToDevice, h->stream));
-      if (!support_fast_bounds(h->fast, h->stream, last ? nullptr : d_win, r > 0 ? d_wout : nullptr))
-        return NGHMM_ERR_HIP;
-      if (r > 0) HIP_TRY(hipMemcpyAsync(vec.data(), d_wout, I * 2 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+      if ((rc = relay.backward_begin(r, nullptr)) || (rc = relay.backward_end(r))) return rc;
       HIP_TRY(sync_stream(h));
     }
   } else {
@@ -419,21 +370,7 @@ int nghmm_chain_tract_bounds(nghmm_t** hs, int n_handles, const nghmm_tract* tra
                              const uint64_t* anchor, const double* levels, uint32_t n_levels,
                              nghmm_tract_bound* out, uint64_t* start, uint64_t* end) {
   g_last_error.clear();
-  if (!hs || n_handles < 1) {
-    set_error("nghmm_chain_tract_bounds: no handles");
-    return NGHMM_ERR_ARG;
-  }
-  if (n_handles > 1) {
-    struct ChainCtx* cx = hs[0] ? hs[0]->chain : nullptr;
-    bool ok = cx != nullptr;
-    for (int r = 0; ok && r < n_handles; ++r)
-      ok = hs[r] && hs[r]->chain == cx && hs[r]->fast.shard.rank == (uint32_t)r &&
-           hs[r]->fast.shard.world == (uint32_t)n_handles;
-    if (!ok) {
-      set_error("nghmm_chain_tract_bounds: call nghmm_chain_setup on these handles first");
-      return NGHMM_ERR_ARG;
-    }
-  }
-  return bounds_impl(hs, n_handles, tracts, n, anchor, levels, n_levels, out, start, end,
-                     "nghmm_chain_tract_bounds");
+  const char* who = "nghmm_chain_tract_bounds";
+  const int rc = chain_entry_check(hs, n_handles, who);
+  return rc ? rc : bounds_impl(hs, n_handles, tracts, n, anchor, levels, n_levels, out, start, end, who);
 }

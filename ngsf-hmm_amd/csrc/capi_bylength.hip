@@ -9,11 +9,9 @@
 // (implementation of include/nghmm.h; capi_internal.hpp has the handle and the shared helpers.)
 #include <cstddef>
 
-#include "capi_internal.hpp"
+#include "capi_chain.hpp"
 #include "kernels_bounds.hpp"
 #include "kernels_bylength.hpp"
-#include "kernels_sample.hpp"
-#include "kernels_support.hpp"
 
 static_assert(sizeof(nghmm_bylength_stat) == sizeof(ByLenRec) &&
                   offsetof(nghmm_bylength_stat, tracts) == offsetof(ByLenRec, tracts) &&
@@ -31,11 +29,11 @@ struct Shard {
   // device scratch (h->d_byl)
   ExpectRegion* d_reg = nullptr;
   ByLenRec *d_piece = nullptr, *d_rec = nullptr;
+  uint8_t* d_ch = nullptr;           // fast mode: the lane-chunk maps and scans, ch
   ByLenChunks ch{};
   uint32_t* d_btab = nullptr;
   double *d_cum = nullptr, *d_cum_halo = nullptr, *d_qmax = nullptr;
-  double *d_vin = nullptr, *d_vout = nullptr, *d_win = nullptr, *d_wout = nullptr;
-  double *d_cin = nullptr, *d_cout = nullptr;
+  double *d_cin = nullptr, *d_cout = nullptr;   // M and D at the cut, beside the relay's vectors
   double *d_hq = nullptr, *d_hrem = nullptr;   // the halo this shard reads, [I][H]
   uint32_t* d_hn = nullptr;
   double *d_oq = nullptr, *d_orem = nullptr;   // the halo this shard gives, [I][H of the shard in front]
@@ -45,13 +43,8 @@ struct Shard {
 int bylength_impl(nghmm_t** hs, int n, int what, uint32_t K, const double* min_len, uint64_t n_regions,
                   const uint64_t* begin, const uint64_t* end, nghmm_bylength_stat* stats, const char* who) {
   uint64_t S_tot = 0;
-  for (int r = 0; r < n; ++r) {
-    if (!hs[r] || !hs[r]->loaded) {
-      set_error("%s: the handle holds no data", who);
-      return NGHMM_ERR_ARG;
-    }
-    S_tot += hs[r]->S;
-  }
+  int rc;
+  if ((rc = chain_check_loaded(hs, n, who, &S_tot))) return rc;
   if (what & ~NGHMM_BYLENGTH_MB) {
     set_error("%s: what = %d is not 0 or NGHMM_BYLENGTH_MB", who, what);
     return NGHMM_ERR_ARG;
@@ -73,13 +66,9 @@ int bylength_impl(nghmm_t** hs, int n, int what, uint32_t K, const double* min_l
     }
   }
   const uint64_t I = hs[0]->I, R = n_regions;
-  int rc;
   if ((rc = summary_check_regions(S_tot, I, R, begin, end, stats, nullptr, who))) return rc;
   const bool fast = hs[0]->mode == NGHMM_MODE_FAST;
-  if (n > 1 && !fast) {
-    set_error("%s: site shards are a fast-mode layout", who);
-    return NGHMM_ERR_ARG;
-  }
+  if ((rc = chain_check_fast(hs, n, who))) return rc;
   if (S_tot >= 0xfffffff0ull) {
     set_error("%s: %llu sites: the table of window ends holds 32-bit site indices", who,
               (unsigned long long)S_tot);
@@ -150,25 +139,13 @@ int bylength_impl(nghmm_t** hs, int n, int what, uint32_t K, const double* min_l
     }
   }
   // cut the regions at the shard boundaries; number the pieces
-  {
-    for (int r = 0; r < n; ++r) {
-      Shard& x = sh[r];
-      const uint64_t lo = x.base, hi = x.base + hs[r]->S, T = fast ? hs[r]->fast.T : 1;
-      for (uint64_t k = 0; k < R; ++k) {
-        if (end[k] <= lo || begin[k] >= hi) continue;
-        ExpectRegion g;
-        g.begin = std::max(begin[k], lo) - lo;
-        g.end = std::min(end[k], hi) - lo;
-        g.piece0 = x.n_pieces;
-        g.pad = 0;
-        if (fast) x.n_pieces += expect_pieces(g.begin, g.end, T);
-        x.reg.push_back(g);
-        x.owner.push_back(k);
-      }
-      x.rec.resize((size_t)I * x.reg.size() * K);
-    }
+  for (int r = 0; r < n; ++r) {
+    Shard& x = sh[r];
+    x.n_pieces = cut_regions(begin, end, R, x.base, x.base + hs[r]->S, fast ? hs[r]->fast.T : 0, x.reg, x.owner);
+    x.rec.resize((size_t)I * x.reg.size() * K);
   }
-  std::vector<double> vec((size_t)I * 2), carry((size_t)I * 2), qmax_h;
+  ChainRelay relay(hs, n);
+  std::vector<double> carry((size_t)I * 2), qmax_h;
   std::vector<uint32_t> tab;
   std::vector<double> cum_il;
   // scratch, the tables, and the forward half: first shard to last
@@ -180,43 +157,28 @@ int bylength_impl(nghmm_t** hs, int n, int what, uint32_t K, const double* min_l
     const uint64_t J = fast ? h->fast.J : 0, Spad = fast ? J * h->fast.T : S;
     const uint64_t Hout = r > 0 ? sh[r - 1].H : 0;
     const uint64_t n_q = fast ? I * h->fast.C : I;
-    const uint64_t b_reg = align256(m * sizeof(ExpectRegion)),
-                   b_piece = align256(I * x.n_pieces * K * sizeof(ByLenRec)),
-                   b_rec = align256(I * m * K * sizeof(ByLenRec)),
-                   b_ch = align256(fast ? bylength_chunk_bytes(I, J) : 0),
-                   b_tab = align256((uint64_t)K * Spad * sizeof(uint32_t)),
-                   b_cum = align256(mb ? Spad * sizeof(double) : 0),
-                   b_cumh = align256(mb ? x.H * sizeof(double) : 0), b_qmax = align256(n_q * sizeof(double)),
-                   b_vec = align256(I * 2 * sizeof(double)), b_h8 = align256(I * x.H * sizeof(double)),
-                   b_h4 = align256(I * x.H * sizeof(uint32_t)), b_o8 = align256(I * Hout * sizeof(double)),
-                   b_o4 = align256(I * Hout * sizeof(uint32_t));
-    if ((rc = h->d_byl.reserve(b_reg + b_piece + b_rec + b_ch + b_tab + b_cum + b_cumh + b_qmax + 6 * b_vec +
-                               2 * b_h8 + b_h4 + 2 * b_o8 + b_o4)))
-      return rc;
+    Carver cv;
+    cv.add(&x.d_reg, m);
+    cv.add(&x.d_piece, I * x.n_pieces * K);
+    cv.add(&x.d_rec, I * m * K);
+    cv.add(&x.d_ch, fast ? bylength_chunk_bytes(I, J) : 0);
+    cv.add(&x.d_btab, (uint64_t)K * Spad);
+    cv.add(&x.d_cum, mb ? Spad : 0);
+    cv.add(&x.d_cum_halo, mb ? x.H : 0);
+    cv.add(&x.d_qmax, n_q);
+    relay.add(cv, r);
+    cv.add(&x.d_cin, I * 2);
+    cv.add(&x.d_cout, I * 2);
+    cv.add(&x.d_hq, I * x.H);
+    cv.add(&x.d_hrem, I * x.H);
+    cv.add(&x.d_hn, I * x.H);
+    cv.add(&x.d_oq, I * Hout);
+    cv.add(&x.d_orem, I * Hout);
+    cv.add(&x.d_on, I * Hout);
+    if ((rc = cv.reserve(h->d_byl))) return rc;
     const uint64_t cells = bylength_cell_count(fast ? &h->fast : nullptr, S, I);
     if ((rc = h->d_byl_cell.reserve(bylength_cell_bytes(cells)))) return rc;
-    uint8_t* p = h->d_byl.p;
-    auto take = [&p](uint64_t bytes) {
-      uint8_t* q = p;
-      p += bytes;
-      return q;
-    };
-    x.d_reg = reinterpret_cast<ExpectRegion*>(take(b_reg));
-    x.d_piece = reinterpret_cast<ByLenRec*>(take(b_piece));
-    x.d_rec = reinterpret_cast<ByLenRec*>(take(b_rec));
-    if (fast) x.ch = bylength_carve_chunks(take(b_ch), I, J);
-    x.d_btab = reinterpret_cast<uint32_t*>(take(b_tab));
-    x.d_cum = reinterpret_cast<double*>(take(b_cum));
-    x.d_cum_halo = reinterpret_cast<double*>(take(b_cumh));
-    x.d_qmax = reinterpret_cast<double*>(take(b_qmax));
-    double** const vecs[6] = {&x.d_vin, &x.d_vout, &x.d_win, &x.d_wout, &x.d_cin, &x.d_cout};
-    for (double** v : vecs) *v = reinterpret_cast<double*>(take(b_vec));
-    x.d_hq = reinterpret_cast<double*>(take(b_h8));
-    x.d_hrem = reinterpret_cast<double*>(take(b_h8));
-    x.d_hn = reinterpret_cast<uint32_t*>(take(b_h4));
-    x.d_oq = reinterpret_cast<double*>(take(b_o8));
-    x.d_orem = reinterpret_cast<double*>(take(b_o8));
-    x.d_on = reinterpret_cast<uint32_t*>(take(b_o4));
+    if (fast) x.ch = bylength_carve_chunks(x.d_ch, I, J);
     // the shard's tables: handle-local ends (S + h in the halo), tile-major in fast mode
     tab.assign((size_t)K * Spad, kByLenNone);
     if (mb) cum_il.assign(Spad, 0.0);
@@ -238,18 +200,7 @@ int bylength_impl(nghmm_t** hs, int n, int what, uint32_t K, const double* min_l
                                h->stream));
     }
     if (m) HIP_TRY(hipMemcpyAsync(x.d_reg, x.reg.data(), m * sizeof(ExpectRegion), hipMemcpyHostToDevice, h->stream));
-    if ((rc = clear_flags(h))) return rc;
-    if (fast) {
-      if ((rc = ensure_emissions(h))) return rc;
-      if (r > 0)
-        HIP_TRY(hipMemcpyAsync(x.d_vin, vec.data(), I * 2 * sizeof(double), hipMemcpyHostToDevice, h->stream));
-      if (!sample_fast_forward(h->fast, h->stream, h->d_indF, h->d_alpha, r ? x.d_vin : nullptr, x.d_vout))
-        return NGHMM_ERR_HIP;
-      if (r + 1 < n)
-        HIP_TRY(hipMemcpyAsync(vec.data(), x.d_vout, I * 2 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    }
-    HIP_TRY(hipGetLastError());
-    if ((rc = check_flags(h))) return rc;   // (waits for the stream: tab and cum_il are free again)
+    if ((rc = relay.forward(r))) return rc;   // (waits for the stream: tab and cum_il are free again)
   }
   // the backward half: last shard to first
   std::vector<double> halo_q, halo_rem;
@@ -264,8 +215,8 @@ int bylength_impl(nghmm_t** hs, int n, int what, uint32_t K, const double* min_l
     const ByLenCells cl = bylength_carve(h->d_byl_cell.p, cells);
     const uint64_t n_q = fast ? I * h->fast.C : I;
     if (fast) {
+      if ((rc = relay.backward_upload(r))) return rc;
       if (!last) {
-        HIP_TRY(hipMemcpyAsync(x.d_win, vec.data(), I * 2 * sizeof(double), hipMemcpyHostToDevice, h->stream));
         HIP_TRY(hipMemcpyAsync(x.d_cin, carry.data(), I * 2 * sizeof(double), hipMemcpyHostToDevice, h->stream));
         if (x.H) {
           HIP_TRY(hipMemcpyAsync(x.d_hq, halo_q.data(), I * x.H * sizeof(double), hipMemcpyHostToDevice, h->stream));
@@ -280,17 +231,14 @@ int bylength_impl(nghmm_t** hs, int n, int what, uint32_t K, const double* min_l
       halo.q = x.d_hq;
       halo.rem = x.d_hrem;
       halo.n = x.d_hn;
-      if (!support_fast_bounds(h->fast, h->stream, last ? nullptr : x.d_win, r > 0 ? x.d_wout : nullptr) ||
-          !bylength_fast_cells(h->fast, h->stream, h->d_indF, h->d_alpha, r > 0, mb, cl, x.ch,
+      if ((rc = relay.backward_bounds(r, who))) return rc;
+      if (!bylength_fast_cells(h->fast, h->stream, h->d_indF, h->d_alpha, r > 0, mb, cl, x.ch,
                                last ? nullptr : x.d_cin, r > 0 ? x.d_cout : nullptr, x.d_qmax) ||
           !bylength_fast_terms(h->fast, h->stream, mb, K, cl, x.d_btab, x.d_cum, x.d_cum_halo, halo, x.d_reg, m,
-                               x.n_pieces, x.d_piece, x.d_rec)) {
-        set_error("%s: the fast layout (T = %llu sites per lane) is not one the walk knows, or a kernel "
-                  "launch failed", who, (unsigned long long)h->fast.T);
-        return NGHMM_ERR_HIP;
-      }
+                               x.n_pieces, x.d_piece, x.d_rec))
+        return fast_layout_error(h, who);
+      if ((rc = relay.backward_end(r))) return rc;
       if (r > 0) {
-        HIP_TRY(hipMemcpyAsync(vec.data(), x.d_wout, I * 2 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
         HIP_TRY(hipMemcpyAsync(carry.data(), x.d_cout, I * 2 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
         const uint64_t Ho = sh[r - 1].H;
         if (Ho) {
@@ -331,13 +279,10 @@ int bylength_impl(nghmm_t** hs, int n, int what, uint32_t K, const double* min_l
         for (uint32_t k = 0; k < K; ++k) {
           const ByLenRec& s = x.rec[(i * m + g) * K + k];
           nghmm_bylength_stat& d = stats[(i * R + o) * K + k];
-          if (!seen[o]) {
-            d.tracts = s.tracts;
-            d.length = s.length;
-          } else {
-            d.tracts += s.tracts;
-            d.length += s.length;
-          }
+          assign_or_add(!seen[o], [&](auto op) {
+            op(d.tracts, s.tracts);
+            op(d.length, s.length);
+          });
         }
       seen[o] = 1;
     }
@@ -359,23 +304,10 @@ int nghmm_chain_ibd_by_length(nghmm_t** hs, int n_handles, int what, uint32_t n_
                               const double* min_length, uint64_t n_regions, const uint64_t* region_begin,
                               const uint64_t* region_end, nghmm_bylength_stat* stats) {
   g_last_error.clear();
-  if (!hs || n_handles < 1) {
-    set_error("nghmm_chain_ibd_by_length: no handles");
-    return NGHMM_ERR_ARG;
-  }
-  if (n_handles > 1) {
-    struct ChainCtx* cx = hs[0] ? hs[0]->chain : nullptr;
-    bool ok = cx != nullptr;
-    for (int r = 0; ok && r < n_handles; ++r)
-      ok = hs[r] && hs[r]->chain == cx && hs[r]->fast.shard.rank == (uint32_t)r &&
-           hs[r]->fast.shard.world == (uint32_t)n_handles;
-    if (!ok) {
-      set_error("nghmm_chain_ibd_by_length: call nghmm_chain_setup on these handles first");
-      return NGHMM_ERR_ARG;
-    }
-  }
-  return bylength_impl(hs, n_handles, what, n_lengths, min_length, n_regions, region_begin, region_end, stats,
-                       "nghmm_chain_ibd_by_length");
+  const char* who = "nghmm_chain_ibd_by_length";
+  const int rc = chain_entry_check(hs, n_handles, who);
+  if (rc) return rc;
+  return bylength_impl(hs, n_handles, what, n_lengths, min_length, n_regions, region_begin, region_end, stats, who);
 }
 
 int nghmm_debug_bylength_qmax(nghmm_t* h, double* qmax) {

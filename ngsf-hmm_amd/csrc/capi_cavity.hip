@@ -7,6 +7,7 @@
 // the first, I x 2 doubles per boundary through the host; every vector is a plain site-by-site
 // recursion (kernels_freqinfo.hip), so the shards continue the single handle's arithmetic bit for
 // bit.  (capi_internal.hpp has the declaration, the handle and the shared helpers.)
+#include "capi_chain_host.hpp"
 #include "capi_internal.hpp"
 #include "kernels_freqinfo.hpp"
 
@@ -22,22 +23,14 @@ struct Carve {
 
 int carve(nghmm_t* h, DevScratch<uint8_t>& own, uint64_t n_seg, uint64_t b_extra, Carve& c) {
   const uint64_t I = h->I, S = h->S;
-  const uint64_t b_vec = align256(I * 2 * sizeof(double));
-  const uint64_t b_cav = align256(S * I * 2 * sizeof(double)), b_seg = align256((n_seg + 1) * sizeof(uint64_t));
-  int rc;
-  if ((rc = own.reserve(2 * b_vec + b_seg + b_cav + b_extra))) return rc;
-  uint8_t* p = own.p;
-  c.vin = reinterpret_cast<double*>(p);
-  p += b_vec;
-  c.vout = reinterpret_cast<double*>(p);
-  p += b_vec;
-  c.seg = reinterpret_cast<uint64_t*>(p);
-  p += b_seg;
+  Carver cv;
+  cv.add(&c.vin, I * 2);
+  cv.add(&c.vout, I * 2);
+  cv.add(&c.seg, n_seg + 1);
+  cv.add(&c.cav, S * I * 2);
+  cv.add(&c.extra, b_extra);
   c.n_seg = n_seg;
-  c.cav = reinterpret_cast<double*>(p);
-  p += b_cav;
-  c.extra = p;
-  return NGHMM_OK;
+  return cv.reserve(own);
 }
 
 }  // namespace

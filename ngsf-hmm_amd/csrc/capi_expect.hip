@@ -8,10 +8,8 @@
 // (implementation of include/nghmm.h; capi_internal.hpp has the handle and the shared helpers.)
 #include <cstddef>
 
-#include "capi_internal.hpp"
+#include "capi_chain.hpp"
 #include "kernels_expect.hpp"
-#include "kernels_sample.hpp"
-#include "kernels_support.hpp"
 
 static_assert(sizeof(nghmm_expect_region) == sizeof(ExpectRec) &&
                   offsetof(nghmm_expect_region, ibd) == offsetof(ExpectRec, ibd) &&
@@ -41,20 +39,14 @@ struct Shard {
   ExpectRec *d_piece = nullptr, *d_rec = nullptr;
   ExpectSite* d_sites = nullptr;
   uint8_t* d_prev = nullptr;
-  double *d_vin = nullptr, *d_vout = nullptr, *d_win = nullptr, *d_wout = nullptr;
 };
 
 int expect_impl(nghmm_t** hs, int n, int what, uint64_t n_regions, const uint64_t* begin,
                 const uint64_t* end, nghmm_expect_region* regions, nghmm_expect_site* sites,
                 const char* who) {
   uint64_t S_tot = 0;
-  for (int r = 0; r < n; ++r) {
-    if (!hs[r] || !hs[r]->loaded) {
-      set_error("%s: the handle holds no data", who);
-      return NGHMM_ERR_ARG;
-    }
-    S_tot += hs[r]->S;
-  }
+  int rc;
+  if ((rc = chain_check_loaded(hs, n, who, &S_tot))) return rc;
   if (what & ~NGHMM_EXPECT_VITERBI) {
     set_error("%s: what = %d is not 0 or NGHMM_EXPECT_VITERBI", who, what);
     return NGHMM_ERR_ARG;
@@ -67,37 +59,18 @@ int expect_impl(nghmm_t** hs, int n, int what, uint64_t n_regions, const uint64_
         return NGHMM_ERR_ARG;
       }
   const uint64_t I = hs[0]->I, R = n_regions;
-  int rc;
   if ((rc = summary_check_regions(S_tot, I, R, begin, end, regions, sites, who))) return rc;
   const bool fast = hs[0]->mode == NGHMM_MODE_FAST;
-  if (n > 1 && !fast) {
-    set_error("%s: site shards are a fast-mode layout", who);
-    return NGHMM_ERR_ARG;
-  }
+  if ((rc = chain_check_fast(hs, n, who))) return rc;
   // cut at the shard boundaries; number the pieces
   std::vector<Shard> sh(n);
-  {
-    uint64_t base = 0;
-    for (int r = 0; r < n; ++r) {
-      Shard& x = sh[r];
-      x.base = base;
-      const uint64_t lo = base, hi = base + hs[r]->S, T = fast ? hs[r]->fast.T : 1;
-      base = hi;
-      for (uint64_t k = 0; k < R; ++k) {
-        if (end[k] <= lo || begin[k] >= hi) continue;
-        ExpectRegion g;
-        g.begin = std::max(begin[k], lo) - lo;
-        g.end = std::min(end[k], hi) - lo;
-        g.piece0 = x.n_pieces;
-        g.pad = 0;
-        if (fast) x.n_pieces += expect_pieces(g.begin, g.end, T);
-        x.reg.push_back(g);
-        x.owner.push_back(k);
-      }
-      x.rec.resize((size_t)I * x.reg.size());
-    }
+  for (int r = 0; r < n; ++r) {
+    Shard& x = sh[r];
+    x.base = r ? sh[r - 1].base + hs[r - 1]->S : 0;
+    x.n_pieces = cut_regions(begin, end, R, x.base, x.base + hs[r]->S, fast ? hs[r]->fast.T : 0, x.reg, x.owner);
+    x.rec.resize((size_t)I * x.reg.size());
   }
-  std::vector<double> vec((size_t)I * 2);
+  ChainRelay relay(hs, n);
   std::vector<uint8_t> state(I);
   // scratch, and the forward half: first shard to last
   for (int r = 0; r < n; ++r) {
@@ -105,49 +78,23 @@ int expect_impl(nghmm_t** hs, int n, int what, uint64_t n_regions, const uint64_
     Shard& x = sh[r];
     if ((rc = use_device(h))) return rc;
     const uint64_t m = x.reg.size();
-    const uint64_t b_reg = align256(m * sizeof(ExpectRegion)),
-                   b_piece = align256(I * x.n_pieces * sizeof(ExpectRec)),
-                   b_rec = align256(I * m * sizeof(ExpectRec)),
-                   b_sites = align256(sites ? h->S * sizeof(ExpectSite) : 0), b_prev = align256(I),
-                   b_vec = align256(I * 2 * sizeof(double));
-    if ((rc = h->d_expt.reserve(b_reg + b_piece + b_rec + b_sites + b_prev + 4 * b_vec))) return rc;
+    Carver cv;
+    cv.add(&x.d_reg, m);
+    cv.add(&x.d_piece, I * x.n_pieces);
+    cv.add(&x.d_rec, I * m);
+    cv.add(&x.d_sites, sites ? h->S : 0);
+    cv.add(&x.d_prev, I);
+    relay.add(cv, r);
+    if ((rc = cv.reserve(h->d_expt))) return rc;
     if (sites && (rc = h->d_expt_cell.reserve(expect_cell_doubles(fast ? &h->fast : nullptr, h->S, I))))
       return rc;
-    uint8_t* p = h->d_expt.p;
-    x.d_reg = reinterpret_cast<ExpectRegion*>(p);
-    p += b_reg;
-    x.d_piece = reinterpret_cast<ExpectRec*>(p);
-    p += b_piece;
-    x.d_rec = reinterpret_cast<ExpectRec*>(p);
-    p += b_rec;
-    x.d_sites = reinterpret_cast<ExpectSite*>(p);
-    p += b_sites;
-    x.d_prev = p;
-    p += b_prev;
-    double** const vecs[4] = {&x.d_vin, &x.d_vout, &x.d_win, &x.d_wout};
-    for (double** v : vecs) {
-      *v = reinterpret_cast<double*>(p);
-      p += b_vec;
-    }
     if (m) HIP_TRY(hipMemcpyAsync(x.d_reg, x.reg.data(), m * sizeof(ExpectRegion), hipMemcpyHostToDevice, h->stream));
-    if ((rc = clear_flags(h))) return rc;
-    if (fast) {
-      if ((rc = ensure_emissions(h))) return rc;
-      if (r > 0)
-        HIP_TRY(hipMemcpyAsync(x.d_vin, vec.data(), I * 2 * sizeof(double), hipMemcpyHostToDevice, h->stream));
-      if (!sample_fast_forward(h->fast, h->stream, h->d_indF, h->d_alpha, r ? x.d_vin : nullptr, x.d_vout))
-        return NGHMM_ERR_HIP;
-      if (r + 1 < n)
-        HIP_TRY(hipMemcpyAsync(vec.data(), x.d_vout, I * 2 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    }
-    HIP_TRY(hipGetLastError());
-    if ((rc = check_flags(h))) return rc;   // (waits for the stream)
+    if ((rc = relay.forward(r))) return rc;
   }
   // the backward half: last shard to first
   for (int r = n - 1; r >= 0; --r) {
     nghmm_t* h = hs[r];
     Shard& x = sh[r];
-    const bool last = r == n - 1;
     const uint64_t m = x.reg.size();
     // the decoded state at the last site of the shard before (its device, its stream)
     if (vit && r > 0 && (rc = summary_last_state(hs[r - 1], state.data()))) return rc;
@@ -156,18 +103,12 @@ int expect_impl(nghmm_t** hs, int n, int what, uint64_t n_regions, const uint64_
     double* d_cell = sites ? h->d_expt_cell.p : nullptr;
     const uint8_t* path = vit ? h->d_path_sites.p : nullptr;
     if (fast) {
-      if (!last)
-        HIP_TRY(hipMemcpyAsync(x.d_win, vec.data(), I * 2 * sizeof(double), hipMemcpyHostToDevice, h->stream));
-      if (!support_fast_bounds(h->fast, h->stream, last ? nullptr : x.d_win, r > 0 ? x.d_wout : nullptr) ||
-          !expect_fast_walk(h->fast, h->stream, h->d_indF, h->d_alpha, r > 0, path,
+      if ((rc = relay.backward_begin(r, who))) return rc;
+      if (!expect_fast_walk(h->fast, h->stream, h->d_indF, h->d_alpha, r > 0, path,
                             vit && r > 0 ? x.d_prev : nullptr, x.d_reg, m, x.n_pieces, x.d_piece, x.d_rec,
-                            d_cell, x.d_sites)) {
-        set_error("%s: the fast layout (T = %llu sites per lane) is not one the walk knows, or a kernel "
-                  "launch failed", who, (unsigned long long)h->fast.T);
-        return NGHMM_ERR_HIP;
-      }
-      if (r > 0)
-        HIP_TRY(hipMemcpyAsync(vec.data(), x.d_wout, I * 2 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+                            d_cell, x.d_sites))
+        return fast_layout_error(h, who);
+      if ((rc = relay.backward_end(r))) return rc;
     } else {
       launch_expect_exact(h->stream, h->d_eprob, h->d_pos, h->d_fw, h->S, I, h->d_indF, h->d_alpha, path,
                           x.d_reg, m, x.d_rec, d_cell, x.d_sites, h->d_flags);
@@ -192,21 +133,14 @@ int expect_impl(nghmm_t** hs, int n, int what, uint64_t n_regions, const uint64_
       for (uint64_t i = 0; i < I; ++i) {
         const ExpectRec& s = x.rec[i * m + k];
         nghmm_expect_region& o = regions[i * R + g];
-        if (!seen[g]) {
-          o.ibd = s.ibd;
-          o.starts = s.starts;
-          o.switches = s.switches;
-          o.ibd_mb = s.ibd_mb;
-          o.entropy = s.entropy;
-          o.log_p_path = s.log_p_path;
-        } else {
-          o.ibd += s.ibd;
-          o.starts += s.starts;
-          o.switches += s.switches;
-          o.ibd_mb += s.ibd_mb;
-          o.entropy += s.entropy;
-          o.log_p_path += s.log_p_path;
-        }
+        assign_or_add(!seen[g], [&](auto op) {
+          op(o.ibd, s.ibd);
+          op(o.starts, s.starts);
+          op(o.switches, s.switches);
+          op(o.ibd_mb, s.ibd_mb);
+          op(o.entropy, s.entropy);
+          op(o.log_p_path, s.log_p_path);
+        });
       }
       seen[g] = 1;
     }
@@ -226,21 +160,7 @@ int nghmm_chain_ibd_expect(nghmm_t** hs, int n_handles, int what, uint64_t n_reg
                            const uint64_t* region_begin, const uint64_t* region_end,
                            nghmm_expect_region* regions, nghmm_expect_site* sites) {
   g_last_error.clear();
-  if (!hs || n_handles < 1) {
-    set_error("nghmm_chain_ibd_expect: no handles");
-    return NGHMM_ERR_ARG;
-  }
-  if (n_handles > 1) {
-    struct ChainCtx* cx = hs[0] ? hs[0]->chain : nullptr;
-    bool ok = cx != nullptr;
-    for (int r = 0; ok && r < n_handles; ++r)
-      ok = hs[r] && hs[r]->chain == cx && hs[r]->fast.shard.rank == (uint32_t)r &&
-           hs[r]->fast.shard.world == (uint32_t)n_handles;
-    if (!ok) {
-      set_error("nghmm_chain_ibd_expect: call nghmm_chain_setup on these handles first");
-      return NGHMM_ERR_ARG;
-    }
-  }
-  return expect_impl(hs, n_handles, what, n_regions, region_begin, region_end, regions, sites,
-                     "nghmm_chain_ibd_expect");
+  const char* who = "nghmm_chain_ibd_expect";
+  const int rc = chain_entry_check(hs, n_handles, who);
+  return rc ? rc : expect_impl(hs, n_handles, what, n_regions, region_begin, region_end, regions, sites, who);
 }

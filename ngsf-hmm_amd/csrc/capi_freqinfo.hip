@@ -9,7 +9,7 @@
 // shards'.  The walks and their vectors are cavity_walks (capi_cavity.hip), which
 // capi_genosmooth.hip drives too; what this file makes of the weights is the site pass.
 // (implementation of include/nghmm.h; capi_internal.hpp has the handle and the shared helpers.)
-#include "capi_internal.hpp"
+#include "capi_chain.hpp"
 #include "kernels_freqinfo.hpp"
 
 static_assert(sizeof(nghmm_freq_stat) == 32, "nghmm_freq_stat is 32 bytes");
@@ -19,11 +19,8 @@ namespace {
 
 int freqinfo_impl(nghmm_t** hs, int n, uint32_t n_levels, const double* levels, nghmm_freq_stat* stats,
                   double* curve, double* cavity, const char* who) {
-  for (int r = 0; r < n; ++r)
-    if (!hs[r] || !hs[r]->loaded) {
-      set_error("%s: the handle holds no data", who);
-      return NGHMM_ERR_ARG;
-    }
+  int rc;
+  if ((rc = chain_check_loaded(hs, n, who))) return rc;
   if (n_levels > FREQINFO_MAX_LEVELS) {
     set_error("%s: n_levels = %u: at most %u levels", who, n_levels, FREQINFO_MAX_LEVELS);
     return NGHMM_ERR_ARG;
@@ -47,10 +44,7 @@ int freqinfo_impl(nghmm_t** hs, int n, uint32_t n_levels, const double* levels, 
     lv.f[k] = levels[k];
   }
   const bool fast = hs[0]->mode == NGHMM_MODE_FAST;
-  if (n > 1 && !fast) {
-    set_error("%s: site shards are a fast-mode layout", who);
-    return NGHMM_ERR_ARG;
-  }
+  if ((rc = chain_check_fast(hs, n, who))) return rc;
   const uint64_t I = hs[0]->I;
   uint64_t S_tot = 0;
   std::vector<uint64_t> base(n);
@@ -114,20 +108,7 @@ int nghmm_freq_info(nghmm_t* h, uint32_t n_levels, const double* levels, nghmm_f
 int nghmm_chain_freq_info(nghmm_t** hs, int n_handles, uint32_t n_levels, const double* levels,
                           nghmm_freq_stat* stats, double* curve, double* cavity) {
   g_last_error.clear();
-  if (!hs || n_handles < 1) {
-    set_error("nghmm_chain_freq_info: no handles");
-    return NGHMM_ERR_ARG;
-  }
-  if (n_handles > 1) {
-    struct ChainCtx* cx = hs[0] ? hs[0]->chain : nullptr;
-    bool ok = cx != nullptr;
-    for (int r = 0; ok && r < n_handles; ++r)
-      ok = hs[r] && hs[r]->chain == cx && hs[r]->fast.shard.rank == (uint32_t)r &&
-           hs[r]->fast.shard.world == (uint32_t)n_handles;
-    if (!ok) {
-      set_error("nghmm_chain_freq_info: call nghmm_chain_setup on these handles first");
-      return NGHMM_ERR_ARG;
-    }
-  }
-  return freqinfo_impl(hs, n_handles, n_levels, levels, stats, curve, cavity, "nghmm_chain_freq_info");
+  const char* who = "nghmm_chain_freq_info";
+  const int rc = chain_entry_check(hs, n_handles, who);
+  return rc ? rc : freqinfo_impl(hs, n_handles, n_levels, levels, stats, curve, cavity, who);
 }

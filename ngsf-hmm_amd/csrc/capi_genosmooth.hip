@@ -8,7 +8,7 @@
 // (implementation of include/nghmm.h; capi_internal.hpp has the handle and the shared helpers.)
 #include <cstddef>
 
-#include "capi_internal.hpp"
+#include "capi_chain.hpp"
 #include "kernels_genosmooth.hpp"
 
 static_assert(sizeof(nghmm_geno_site_stat) == sizeof(GenoSiteRec) &&
@@ -41,20 +41,14 @@ struct Plan {
 int genosmooth_impl(nghmm_t** hs, int n, uint64_t R, const uint64_t* begin, const uint64_t* end,
                     nghmm_geno_region_stat* regions, nghmm_geno_site_stat* sites, double* post,
                     uint8_t* call, const char* who) {
-  for (int r = 0; r < n; ++r)
-    if (!hs[r] || !hs[r]->loaded) {
-      set_error("%s: the handle holds no data", who);
-      return NGHMM_ERR_ARG;
-    }
+  int rc;
+  if ((rc = chain_check_loaded(hs, n, who))) return rc;
   if (!regions && !sites && !post && !call) {
     set_error("%s: regions, sites, post and call are all NULL: nothing is asked for", who);
     return NGHMM_ERR_ARG;
   }
   const bool fast = hs[0]->mode == NGHMM_MODE_FAST;
-  if (n > 1 && !fast) {
-    set_error("%s: site shards are a fast-mode layout", who);
-    return NGHMM_ERR_ARG;
-  }
+  if ((rc = chain_check_fast(hs, n, who))) return rc;
   const uint64_t I = hs[0]->I;
   uint64_t S_tot = 0;
   std::vector<uint64_t> base(n);
@@ -62,7 +56,6 @@ int genosmooth_impl(nghmm_t** hs, int n, uint64_t R, const uint64_t* begin, cons
     base[r] = S_tot;
     S_tot += hs[r]->S;
   }
-  int rc;
   // (the last argument: some output other than the regions, if there is one)
   const void* other = sites ? (const void*)sites : post ? (const void*)post : (const void*)call;
   if ((rc = summary_check_regions(S_tot, I, R, begin, end, regions, other, who))) return rc;
@@ -174,21 +167,7 @@ int nghmm_chain_geno_smooth(nghmm_t** hs, int n_handles, uint64_t n_regions,
                             nghmm_geno_region_stat* regions, nghmm_geno_site_stat* sites,
                             double* post, uint8_t* call) {
   g_last_error.clear();
-  if (!hs || n_handles < 1) {
-    set_error("nghmm_chain_geno_smooth: no handles");
-    return NGHMM_ERR_ARG;
-  }
-  if (n_handles > 1) {
-    struct ChainCtx* cx = hs[0] ? hs[0]->chain : nullptr;
-    bool ok = cx != nullptr;
-    for (int r = 0; ok && r < n_handles; ++r)
-      ok = hs[r] && hs[r]->chain == cx && hs[r]->fast.shard.rank == (uint32_t)r &&
-           hs[r]->fast.shard.world == (uint32_t)n_handles;
-    if (!ok) {
-      set_error("nghmm_chain_geno_smooth: call nghmm_chain_setup on these handles first");
-      return NGHMM_ERR_ARG;
-    }
-  }
-  return genosmooth_impl(hs, n_handles, n_regions, region_begin, region_end, regions, sites, post, call,
-                         "nghmm_chain_geno_smooth");
+  const char* who = "nghmm_chain_geno_smooth";
+  const int rc = chain_entry_check(hs, n_handles, who);
+  return rc ? rc : genosmooth_impl(hs, n_handles, n_regions, region_begin, region_end, regions, sites, post, call, who);
 }

@@ -3,7 +3,7 @@
 // produce the jet of their site range; the host multiplies them in rank order with the routine
 // the device uses (kernels_info.hpp: jet_mul) and closes once.
 // (implementation of include/nghmm.h; capi_internal.hpp has the handle and the shared helpers.)
-#include "capi_internal.hpp"
+#include "capi_chain.hpp"
 #include "kernels_info.hpp"
 
 static_assert(sizeof(nghmm_info) == 48, "nghmm_info is 48 bytes");
@@ -13,21 +13,15 @@ namespace {
 
 int info_impl(nghmm_t** hs, int n, const double* F, const double* alpha, nghmm_info* out,
               const char* who) {
-  for (int r = 0; r < n; ++r)
-    if (!hs[r] || !hs[r]->loaded) {
-      set_error("%s: the handle holds no data", who);
-      return NGHMM_ERR_ARG;
-    }
+  int rc;
+  if ((rc = chain_check_loaded(hs, n, who))) return rc;
   if (!out || (F == nullptr) != (alpha == nullptr)) {
     set_error("%s: out %s, F %s, alpha %s: out is needed, and F and alpha both or neither", who,
               out ? "given" : "NULL", F ? "given" : "NULL", alpha ? "given" : "NULL");
     return NGHMM_ERR_ARG;
   }
   const bool fast = hs[0]->mode == NGHMM_MODE_FAST;
-  if (n > 1 && !fast) {
-    set_error("%s: site shards are a fast-mode layout", who);
-    return NGHMM_ERR_ARG;
-  }
+  if ((rc = chain_check_fast(hs, n, who))) return rc;
   const uint64_t I = hs[0]->I;
   if (F)
     for (uint64_t i = 0; i < I; ++i)   // the box of EM.cpp:424-438; NaN fails every comparison
@@ -37,7 +31,6 @@ int info_impl(nghmm_t** hs, int n, const double* F, const double* alpha, nghmm_i
         return NGHMM_ERR_ARG;
       }
   std::vector<double> jets(n > 1 ? (size_t)n * I * kJetShardDoubles : 0), Fh;
-  int rc;
   for (int r = 0; r < n; ++r) {
     nghmm_t* h = hs[r];
     if ((rc = use_device(h))) return rc;
@@ -103,19 +96,7 @@ int nghmm_obs_info(nghmm_t* h, const double* F, const double* alpha, nghmm_info*
 
 int nghmm_chain_obs_info(nghmm_t** hs, int n, const double* F, const double* alpha, nghmm_info* out) {
   g_last_error.clear();
-  if (!hs || n < 1) {
-    set_error("nghmm_chain_obs_info: no handles");
-    return NGHMM_ERR_ARG;
-  }
-  if (n > 1) {
-    struct ChainCtx* cx = hs[0] ? hs[0]->chain : nullptr;
-    bool ok = cx != nullptr;
-    for (int r = 0; ok && r < n; ++r) ok = hs[r] && hs[r]->chain == cx && hs[r]->fast.shard.rank == (uint32_t)r &&
-                                           hs[r]->fast.shard.world == (uint32_t)n;
-    if (!ok) {
-      set_error("nghmm_chain_obs_info: call nghmm_chain_setup on these handles first");
-      return NGHMM_ERR_ARG;
-    }
-  }
-  return info_impl(hs, n, F, alpha, out, "nghmm_chain_obs_info");
+  const char* who = "nghmm_chain_obs_info";
+  const int rc = chain_entry_check(hs, n, who);
+  return rc ? rc : info_impl(hs, n, F, alpha, out, who);
 }

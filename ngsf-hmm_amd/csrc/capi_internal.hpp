@@ -1,7 +1,6 @@
 // capi_internal.hpp -- what the translation units of the C ABI share: the handle, error plumbing,
-// and the helpers every entry point uses.  nghmm_capi.hip (handle life cycle, single-handle EM),
-// capi_load.hip (loaders), capi_output.hip (read-back and output formatting), capi_tracts.hip, capi_sample.hip, capi_info.hip, capi_summary.hip, capi_sharing.hip, capi_support.hip, capi_bounds.hip, capi_cavity.hip, capi_freqinfo.hip, capi_genosmooth.hip, capi_expect.hip, capi_moments.hip, capi_bylength.hip and
-// capi_multi.hip (individual shards, site shards, groups and chains of handles) implement include/nghmm.h.
+// and the helpers every entry point uses.  nghmm_capi.hip and the capi_*.hip files, each of which
+// says in its first lines which calls it holds, implement include/nghmm.h.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -24,6 +23,7 @@
 #include "../../include/nghmm.h"
 #include "../../include/nghmm_debug.h"
 #include "bfgs_batch.hpp"
+#include "capi_chain_host.hpp"   // align256
 #include "capi_owners.hpp"
 #include "kernels.hpp"
 #include "kernels_fast.hpp"
@@ -210,9 +210,6 @@ struct nghmm_handle {
 };
 
 namespace capi {
-
-// a carved scratch keeps every part 256-byte aligned
-inline uint64_t align256(uint64_t n) { return (n + 255) & ~255ull; }
 
 hipError_t sync_stream(nghmm_t* h);
 int use_device(nghmm_t* h);

@@ -9,7 +9,7 @@
 // (implementation of include/nghmm.h; capi_internal.hpp has the handle and the shared helpers.)
 #include <cstddef>
 
-#include "capi_internal.hpp"
+#include "capi_chain.hpp"
 #include "kernels_moments.hpp"
 
 static_assert(sizeof(nghmm_moment_region) == sizeof(MomentRec) &&
@@ -83,13 +83,8 @@ void build_tables(const std::vector<Seg>& segs, uint64_t J, uint64_t T, Tables& 
 int moments_impl(nghmm_t** hs, int n, int what, uint64_t n_regions, const uint64_t* begin,
                  const uint64_t* end, nghmm_moment_region* regions, const char* who) {
   uint64_t S_tot = 0;
-  for (int r = 0; r < n; ++r) {
-    if (!hs[r] || !hs[r]->loaded) {
-      set_error("%s: the handle holds no data", who);
-      return NGHMM_ERR_ARG;
-    }
-    S_tot += hs[r]->S;
-  }
+  int rc;
+  if ((rc = chain_check_loaded(hs, n, who, &S_tot))) return rc;
   if (what & ~NGHMM_MOMENTS_MB) {
     set_error("%s: what = %d is not 0 or NGHMM_MOMENTS_MB", who, what);
     return NGHMM_ERR_ARG;
@@ -101,23 +96,21 @@ int moments_impl(nghmm_t** hs, int n, int what, uint64_t n_regions, const uint64
     return NGHMM_ERR_ARG;
   }
   const uint64_t I = hs[0]->I, R = n_regions;
-  int rc;
   if ((rc = summary_check_regions(S_tot, I, R, begin, end, regions, nullptr, who))) return rc;
   const bool fast = hs[0]->mode == NGHMM_MODE_FAST;
   const bool mb = (what & NGHMM_MOMENTS_MB) != 0;
-  if (n > 1 && !fast) {
-    set_error("%s: site shards are a fast-mode layout", who);
-    return NGHMM_ERR_ARG;
-  }
+  if ((rc = chain_check_fast(hs, n, who))) return rc;
   if (!fast) {
     nghmm_t* h = hs[0];
     if ((rc = use_device(h))) return rc;
-    const uint64_t b_reg = align256(R * 2 * sizeof(uint64_t)), b_bw = align256(R * 2 * I * sizeof(double)),
-                   b_out = align256(I * R * sizeof(MomentRec));
-    if ((rc = h->d_mom.reserve(b_reg + b_bw + b_out))) return rc;
-    uint64_t* d_reg = reinterpret_cast<uint64_t*>(h->d_mom.p);
-    double* d_bw = reinterpret_cast<double*>(h->d_mom.p + b_reg);
-    MomentRec* d_out = reinterpret_cast<MomentRec*>(h->d_mom.p + b_reg + b_bw);
+    uint64_t* d_reg;
+    double* d_bw;
+    MomentRec* d_out;
+    Carver cv;
+    cv.add(&d_reg, R * 2);
+    cv.add(&d_bw, R * 2 * I);
+    cv.add(&d_out, I * R);
+    if ((rc = cv.reserve(h->d_mom))) return rc;
     std::vector<uint64_t> reg(R * 2);
     for (uint64_t k = 0; k < R; ++k) {
       reg[2 * k] = begin[k];
@@ -172,30 +165,21 @@ int moments_impl(nghmm_t** hs, int n, int what, uint64_t n_regions, const uint64
     Tables tb;
     build_tables(segs, fs.J, fs.T, tb);
     const uint32_t n_seg = (uint32_t)segs.size(), P = (uint32_t)(tb.piece_end.size() - 1);
-    const uint64_t b_cp = align256((fs.J + 1) * sizeof(uint32_t)), b_pe = align256(((uint64_t)P + 1) * sizeof(uint64_t)),
-                   b_sp = align256(((uint64_t)n_seg + 1) * sizeof(uint32_t)),
-                   b_sr = align256((uint64_t)n_seg * sizeof(int32_t)),
-                   b_piece = align256(I * P * kCJetDoubles * sizeof(double)),
-                   b_seg = align256(I * n_seg * kCJetDoubles * sizeof(double)),
-                   b_bw = align256(((uint64_t)n_seg + 1) * 2 * I * sizeof(double)),
-                   b_out = align256(I * R * sizeof(MomentRec));
-    if ((rc = h->d_mom.reserve(b_cp + b_pe + b_sp + b_sr + b_piece + b_seg + b_bw + b_out))) return rc;
-    uint8_t* p = h->d_mom.p;
-    uint32_t* d_cp = reinterpret_cast<uint32_t*>(p);
-    p += b_cp;
-    uint64_t* d_pe = reinterpret_cast<uint64_t*>(p);
-    p += b_pe;
-    uint32_t* d_sp = reinterpret_cast<uint32_t*>(p);
-    p += b_sp;
-    int32_t* d_sr = reinterpret_cast<int32_t*>(p);
-    p += b_sr;
-    double* d_piece = reinterpret_cast<double*>(p);
-    p += b_piece;
-    double* d_seg = reinterpret_cast<double*>(p);
-    p += b_seg;
-    double* d_bw = reinterpret_cast<double*>(p);
-    p += b_bw;
-    MomentRec* d_out = reinterpret_cast<MomentRec*>(p);
+    uint32_t *d_cp, *d_sp;
+    uint64_t* d_pe;
+    int32_t* d_sr;
+    double *d_piece, *d_seg, *d_bw;
+    MomentRec* d_out;
+    Carver cv;
+    cv.add(&d_cp, fs.J + 1);
+    cv.add(&d_pe, (uint64_t)P + 1);
+    cv.add(&d_sp, (uint64_t)n_seg + 1);
+    cv.add(&d_sr, (uint64_t)n_seg);
+    cv.add(&d_piece, I * P * kCJetDoubles);
+    cv.add(&d_seg, I * n_seg * kCJetDoubles);
+    cv.add(&d_bw, ((uint64_t)n_seg + 1) * 2 * I);
+    cv.add(&d_out, I * R);
+    if ((rc = cv.reserve(h->d_mom))) return rc;
     HIP_TRY(hipMemcpyAsync(d_cp, tb.chunk_piece.data(), (fs.J + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(hipMemcpyAsync(d_pe, tb.piece_end.data(), ((uint64_t)P + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(hipMemcpyAsync(d_sp, tb.seg_piece.data(), ((uint64_t)n_seg + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
@@ -256,21 +240,7 @@ int nghmm_chain_ibd_moments(nghmm_t** hs, int n_handles, int what, uint64_t n_re
                             const uint64_t* region_begin, const uint64_t* region_end,
                             nghmm_moment_region* regions) {
   g_last_error.clear();
-  if (!hs || n_handles < 1) {
-    set_error("nghmm_chain_ibd_moments: no handles");
-    return NGHMM_ERR_ARG;
-  }
-  if (n_handles > 1) {
-    struct ChainCtx* cx = hs[0] ? hs[0]->chain : nullptr;
-    bool ok = cx != nullptr;
-    for (int r = 0; ok && r < n_handles; ++r)
-      ok = hs[r] && hs[r]->chain == cx && hs[r]->fast.shard.rank == (uint32_t)r &&
-           hs[r]->fast.shard.world == (uint32_t)n_handles;
-    if (!ok) {
-      set_error("nghmm_chain_ibd_moments: call nghmm_chain_setup on these handles first");
-      return NGHMM_ERR_ARG;
-    }
-  }
-  return moments_impl(hs, n_handles, what, n_regions, region_begin, region_end, regions,
-                      "nghmm_chain_ibd_moments");
+  const char* who = "nghmm_chain_ibd_moments";
+  const int rc = chain_entry_check(hs, n_handles, who);
+  return rc ? rc : moments_impl(hs, n_handles, what, n_regions, region_begin, region_end, regions, who);
 }

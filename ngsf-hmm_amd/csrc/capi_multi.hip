@@ -572,6 +572,8 @@ void capi::chain_release(nghmm_t* h) {
 
 namespace {
 
+// (capi_chain.hip: chain_entry_check asks every handle's shard rank and world instead, which a
+// later nghmm_site_shard_setup on a member changes: the two do not accept the same handles)
 bool is_chain(nghmm_t** hs, int n) {
   if (!hs || n < 1 || !hs[0]) return false;
   if (n == 1) return hs[0]->chain == nullptr || hs[0]->chain->hs.size() == 1;

@@ -4,7 +4,7 @@
 // then per batch the sampled states from the last shard to the first; the shards' statistics are
 // merged on the host (seg_merge, the rule the device uses between lane-chunks).
 // (implementation of include/nghmm.h; capi_internal.hpp has the handle and the shared helpers.)
-#include "capi_internal.hpp"
+#include "capi_chain.hpp"
 #include "kernels_sample.hpp"
 
 static_assert(sizeof(nghmm_path_stats) == 32, "nghmm_path_stats is 32 bytes");
@@ -30,26 +30,19 @@ struct Shard {
 
 int sample_impl(nghmm_t** hs, int n, uint64_t seed, uint32_t n_draws, nghmm_path_stats* stats,
                 uint32_t n_keep, uint8_t* paths, const char* who) {
-  for (int r = 0; r < n; ++r)
-    if (!hs[r] || !hs[r]->loaded) {
-      set_error("%s: the handle holds no data", who);
-      return NGHMM_ERR_ARG;
-    }
+  int rc;
+  if ((rc = chain_check_loaded(hs, n, who))) return rc;
   if (n_draws == 0 || n_keep > n_draws || (n_keep > 0) != (paths != nullptr)) {
     set_error("%s: n_draws = %u, n_keep = %u, paths %s: n_draws >= 1, n_keep <= n_draws and paths "
               "NULL exactly when n_keep == 0 are needed", who, n_draws, n_keep, paths ? "given" : "NULL");
     return NGHMM_ERR_ARG;
   }
   const bool fast = hs[0]->mode == NGHMM_MODE_FAST;
-  if (n > 1 && !fast) {
-    set_error("%s: site shards are a fast-mode layout", who);
-    return NGHMM_ERR_ARG;
-  }
+  if ((rc = chain_check_fast(hs, n, who))) return rc;
   const uint64_t I = hs[0]->I;
   const uint32_t keep_batch = std::min(n_keep, kSampleBatch);
   std::vector<Shard> sh(n);
   uint64_t S_tot = 0;
-  int rc;
   // scratch, and the forward half: first shard to last
   std::vector<double> vec((size_t)I * 2);
   for (int r = 0; r < n; ++r) {
@@ -136,19 +129,7 @@ int nghmm_sample_paths(nghmm_t* h, uint64_t seed, uint32_t n_draws, nghmm_path_s
 int nghmm_chain_sample_paths(nghmm_t** hs, int n, uint64_t seed, uint32_t n_draws,
                              nghmm_path_stats* stats, uint32_t n_keep, uint8_t* paths) {
   g_last_error.clear();
-  if (!hs || n < 1) {
-    set_error("nghmm_chain_sample_paths: no handles");
-    return NGHMM_ERR_ARG;
-  }
-  if (n > 1) {
-    struct ChainCtx* cx = hs[0] ? hs[0]->chain : nullptr;
-    bool ok = cx != nullptr;
-    for (int r = 0; ok && r < n; ++r) ok = hs[r] && hs[r]->chain == cx && hs[r]->fast.shard.rank == (uint32_t)r &&
-                                           hs[r]->fast.shard.world == (uint32_t)n;
-    if (!ok) {
-      set_error("nghmm_chain_sample_paths: call nghmm_chain_setup on these handles first");
-      return NGHMM_ERR_ARG;
-    }
-  }
-  return sample_impl(hs, n, seed, n_draws, stats, n_keep, paths, "nghmm_chain_sample_paths");
+  const char* who = "nghmm_chain_sample_paths";
+  const int rc = chain_entry_check(hs, n, who);
+  return rc ? rc : sample_impl(hs, n, seed, n_draws, stats, n_keep, paths, who);
 }

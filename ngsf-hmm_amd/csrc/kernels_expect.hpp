@@ -6,6 +6,7 @@
 
 #include <cstdint>
 
+#include "expect_region.hpp"   // ExpectRegion, expect_pieces
 #include "kernels_fast.hpp"
 
 namespace nghmm {
@@ -22,19 +23,6 @@ struct ExpectSite {
   double on, off, ibd, entropy;
 };
 static_assert(sizeof(ExpectSite) == 32, "nghmm_expect_site is 32 bytes");
-
-// A region of one handle, in handle-local sites, half-open; the regions are sorted and disjoint and
-// the same for every individual.  Fast mode: piece0 = slot of the region's first piece within an
-// individual's pieces (one piece per lane-chunk the region touches).
-struct ExpectRegion {
-  uint64_t begin, end, piece0, pad;
-};
-static_assert(sizeof(ExpectRegion) == 32, "ExpectRegion");
-
-// pieces of a region [begin, end) in a layout of T sites per lane
-__host__ __device__ inline uint64_t expect_pieces(uint64_t begin, uint64_t end, uint64_t T) {
-  return (end - 1) / T - begin / T + 1;
-}
 
 // doubles of per-cell scratch that the site records need (fast mode: [C T][I][4][64]; exact mode:
 // [S][I][4]): on, off, ibd, h of every cell
