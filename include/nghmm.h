@@ -1072,6 +1072,76 @@ int nghmm_chain_ibd_by_length(nghmm_t** hs, int n_handles, int what, uint32_t n_
                               const double* min_length, uint64_t n_regions, const uint64_t* region_begin,
                               const uint64_t* region_end, nghmm_bylength_stat* stats);
 
+/* ---- the longest IBD tract ----
+ * Per individual, region and threshold L_k the probability that SOME IBD run of the region is of
+ * length >= L_k, and that none is, exactly, at the handle's CURRENT indF, alpha and freq.  (The
+ * tracts of nghmm_ibd_by_length bound p_any from above only -- Markov's inequality.)  Notation of
+ * nghmm_ibd_expect / nghmm_ibd_by_length: pi_s(l) the posterior of state l at site s; r_s(k, l) =
+ * P(z_s = l | z_{s-1} = k, y), each entry from its own product, 0 for 0/0; rho_s = r_s(1, 1), 0 at a
+ * chromosome start, and the step into s is BLOCKED iff rho_s == 0.  Chromosome starts, d_s, cum_s,
+ * len(a, b), the thresholds (1 <= K <= 8, strictly increasing; whole numbers of sites >= 1, or with
+ * NGHMM_LONGEST_MB finite and >= 0 Mb) and the table b_k(a) are nghmm_ibd_by_length's.
+ *
+ * For a region [lo, hi) (nghmm_ibd_summary's regions) a RUN is a maximal stretch of z = 1 INSIDE
+ * the region, cut at chromosome starts and at the region's two edges; over whole chromosomes it is
+ * a tract of nghmm_path_stats.  Per threshold, over the sites of the region inside one chromosome,
+ * with N the mass with z_s = 0 and no hit yet, V the mass inside a run that has not reached L_k
+ * and Hit the absorbed mass:
+ *   s = lo:  N = pi_lo(0);  tau_lo = pi_lo(1);  V = tau_lo - G_lo
+ *   s > lo:  tau_s = N r_s(0, 1);  N' = N r_s(0, 0) + V r_s(1, 0);  V' = V rho_s + tau_s - G_s (>= 0)
+ *   G_s = sum over a >= lo with b_k(a) = s of tau_a W(a, s),  W(a, s) = prod_{t = a+1..s} rho_t
+ *   Hit += G_s;   p_any = Hit(hi - 1),   p_none = N(hi - 1) + V(hi - 1)  (its own sum, not 1 - p_any)
+ * Chromosomes are independent given the parameters: a region's parts per chromosome are combined
+ * in site order, any = any_prev + none_prev any_part, none = none_prev none_part.  pi is formed at
+ * a chromosome's first site from q e beta normalised and propagated from there, pi_s(l) =
+ * pi_{s-1}(0) r_s(0, l) + pi_{s-1}(1) r_s(1, l), the same operations wherever the sites are cut.
+ * At L = 1 site (and at 0 Mb) a one-site region gives p_any = pi_s(1).  p_any is non-increasing
+ * in k.  A state the data exclude gives exact zeros; nothing is NaN; a threshold no chromosome
+ * reaches gives p_any = 0 exactly.
+ *
+ * Orders (no float atomics; the same arguments give the same bits on every call, and a region's
+ * record does not depend on which other regions are asked for).  b_k is non-decreasing inside a
+ * chromosome, so a lane keeps a pointer to the oldest unresolved start and a ring of (tau_a, Q_a)
+ * of the starts since; the starts that resolve at s are added to G_s oldest first; a blocked step
+ * discards the ring.  W(a, s) = exp(Q_s - Q_a) with Q the running sum of ln rho (from the small
+ * side, as nghmm_ibd_expect), restarted from 0 at every blocked step and at a part's first site:
+ * nghmm_ibd_by_length's rule and accuracy, an absolute error of about 2^-53 max|Q| in the
+ * exponent.  p_none is accurate to an ABSOLUTE error of that size, not a relative one.  Both modes
+ * walk one lane per (individual, chromosome part of the handle): right to left beta and the steps
+ * r_s, left to right the recursion, a threshold's operations not depending on the other thresholds
+ * (they may share a lane or have lanes of their own: the same bits); fast mode
+ * in linear space with power-of-two rescaling of beta, exact mode with beta and r_s in log space
+ * through detmath.h.  The parts of a region are combined on the host.
+ *
+ * NGHMM_ERR_ARG with a message as nghmm_ibd_by_length.  Self-contained and read-only exactly like
+ * nghmm_freq_info: an EM iteration after the call gives the bits it would have given without it.
+ * Device scratch, kept by the handle and allocated on first use (NGHMM_ERR_NOMEM when it cannot be
+ * had): 40 bytes per cell (the four steps and ln rho); per individual 16 bytes times the sum over
+ * the handle's chromosome parts and the thresholds of the longest window b_k(a) - a + 1 of that
+ * threshold in that part; 4 n_lengths bytes per site of the whole data for b_k; 16 n_lengths per
+ * (individual, region part).   */
+enum { NGHMM_LONGEST_MB = 1 };
+typedef struct nghmm_longest_stat {  /* 16 bytes; one per (individual, region, threshold) */
+  double p_any;   /* P(some run of the region has length >= L_k | y) */
+  double p_none;  /* P(no run has), from its own sum */
+} nghmm_longest_stat;
+#ifdef __cplusplus
+static_assert(sizeof(nghmm_longest_stat) == 16, "record size");
+#endif
+/* stats [I][n_regions][n_lengths] (host) */
+int nghmm_ibd_longest(nghmm_t* h, int what, uint32_t n_lengths, const double* min_length,
+                      uint64_t n_regions, const uint64_t* region_begin, const uint64_t* region_end,
+                      nghmm_longest_stat* stats);
+/* The same over a chain of site shards (nghmm_chain_setup, else NGHMM_ERR_ARG): global site
+ * indices.  beta crosses the cuts right to left, the forward lane state left to right through the
+ * host (pi, Q and per threshold N, V, Hit, the pointer and the ring's live entries); a shard goes
+ * on with the single handle's own operations, so the chain returns the single handle's BYTES, and
+ * no threshold is refused for reaching past a shard.  (Chains of more than one handle are fast
+ * mode only.) */
+int nghmm_chain_ibd_longest(nghmm_t** hs, int n_handles, int what, uint32_t n_lengths,
+                            const double* min_length, uint64_t n_regions, const uint64_t* region_begin,
+                            const uint64_t* region_end, nghmm_longest_stat* stats);
+
 /* ---- pairwise IBD sharing between individuals ----
  * How much IBD two individuals share over the sites [site_begin, site_end): three host matrices
  * [I][I], full and symmetric, reduced on the matrix cores from the decoded path and the

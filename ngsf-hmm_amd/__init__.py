@@ -25,7 +25,8 @@ from .hmm import (NgsFHMM, NgsFHMMError, Group, Chain, MODE_EXACT, MODE_FAST, GE
                   GENO_SITE_STAT_DTYPE, GENO_REGION_STAT_DTYPE, geno_em_freq, het_outside_ibd,
                   EXPECT_VITERBI, EXPECT_REGION_DTYPE, EXPECT_SITE_DTYPE, expect_tract_length,
                   MOMENTS_MB, MOMENT_REGION_DTYPE, moment_sd,
-                  BYLENGTH_MB, BYLENGTH_DTYPE, by_length_classes)
+                  BYLENGTH_MB, BYLENGTH_DTYPE, by_length_classes,
+                  LONGEST_MB, LONGEST_DTYPE, longest_classes)
 from . import simulate
 
 __all__ = ["NgsFHMM", "NgsFHMMError", "Group", "Chain", "MODE_EXACT", "MODE_FAST", "GENO_PACKED", "LD_INTENDED", "EPROB_LD", "library_path",
@@ -38,4 +39,5 @@ __all__ = ["NgsFHMM", "NgsFHMMError", "Group", "Chain", "MODE_EXACT", "MODE_FAST
            "FREQ_STAT_DTYPE", "freq_std_errors", "GENO_SITE_STAT_DTYPE", "GENO_REGION_STAT_DTYPE",
            "geno_em_freq", "het_outside_ibd", "EXPECT_VITERBI", "EXPECT_REGION_DTYPE",
            "EXPECT_SITE_DTYPE", "expect_tract_length", "MOMENTS_MB", "MOMENT_REGION_DTYPE",
-           "moment_sd", "BYLENGTH_MB", "BYLENGTH_DTYPE", "by_length_classes"]
+           "moment_sd", "BYLENGTH_MB", "BYLENGTH_DTYPE", "by_length_classes",
+           "LONGEST_MB", "LONGEST_DTYPE", "longest_classes"]

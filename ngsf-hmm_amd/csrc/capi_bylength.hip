@@ -113,7 +113,9 @@ int bylength_impl(nghmm_t** hs, int n, int what, uint32_t K, const double* min_l
       if (mb) {
         while (b < e && !(cum[b] - cum[a] >= L)) ++b;
       } else {
-        const uint64_t want = a + (uint64_t)L - 1;
+        // (a whole number of sites beyond the data has no window; the cast of one beyond 2^64 is
+        // not defined)
+        const uint64_t want = a + (L >= (double)S_tot ? S_tot : (uint64_t)L) - 1;
         b = want < e ? want : e;
       }
       bt[(size_t)k * S_tot + a] = b < e ? b : ~0ull;

@@ -135,6 +135,11 @@ struct nghmm_handle {
   DevScratch<uint8_t> d_byl;
   DevScratch<uint8_t> d_byl_cell;
   double byl_qmax = 0;   // the largest |Q| of the last call (nghmm_debug_bylength_qmax)
+  // the longest IBD tract (capi_longest.hip): the segments, tables, parts, boundary vectors, lane
+  // states and records; the per-cell planes (40 bytes per cell); the lanes' rings
+  DevScratch<uint8_t> d_lng;
+  DevScratch<uint8_t> d_lng_cell;
+  DevScratch<uint8_t> d_lng_ring;
   DevBuf<double> d_freq_new, d_hap;  // --freq_est 2 as intended: [S], [S][4]
 
   // multi-GPU shard

@@ -42,7 +42,11 @@
 // decode), --ibd_by_length L1,L2,... [--by_length_sites] [--by_length_window N]
 // (PREFIX.ibd.bylength: per individual, chromosome or window of N sites and threshold the expected
 // number of IBD tracts of at least that length -- in Mb, or in sites with --by_length_sites -- that
-// begin there and their expected total length, exactly, made on the device after the final decode).
+// begin there and their expected total length, exactly, made on the device after the final decode),
+// --ibd_longest L1,L2,... [--longest_sites] [--longest_window N] (PREFIX.ibd.longest: per
+// individual, chromosome or window of N sites and threshold the probability that some IBD run there
+// is of at least that length -- in Mb, or in sites with --longest_sites -- and that none is,
+// exactly, made on the device after the final decode).
 // --n_threads (the reference's pool size) sets the host threads used for input normalisation and output
 // formatting; results do not depend on it.
 #include <fcntl.h>
@@ -88,6 +92,8 @@
 #pragma weak nghmm_chain_ibd_moments
 // ... and without the by-length entry: --ibd_by_length then stops with a message
 #pragma weak nghmm_chain_ibd_by_length
+// ... and without the longest-tract entry: --ibd_longest then stops with a message
+#pragma weak nghmm_chain_ibd_longest
 // ... and without the support entries: --ibd_support then stops with a message
 #pragma weak nghmm_tract_support
 #pragma weak nghmm_chain_tract_support
@@ -178,6 +184,13 @@ struct Params {  // ngsF-HMM.hpp:13-52
   bool ibd_by_length = false, by_length_sites = false;
   std::vector<double> by_length;
   uint64_t by_length_window = 0;
+  // --ibd_longest L1,L2,...: PREFIX.ibd.longest after the final decode (nghmm_chain_ibd_longest):
+  // per threshold the probability that some IBD run is of at least that length and that none is,
+  // per individual and chromosome, or with --longest_window N per window of N sites that restarts
+  // at every chromosome start; the thresholds are Mb, or sites with --longest_sites
+  bool ibd_longest = false, longest_sites = false;
+  std::vector<double> longest;
+  uint64_t longest_window = 0;
   // --ibd_support: PREFIX.ibd.support after the final decode -- per Viterbi tract the joint
   // posterior of IBD throughout, its log-odds against non-IBD throughout and the weakest site
   // (nghmm_chain_tract_support)
@@ -1725,6 +1738,51 @@ void write_ibd_by_length(const Params& P, Cohort& C) {
   if (fclose(fh) != 0) fatal(__FUNCTION__, "cannot write the by-length output file!");
 }
 
+// PREFIX.ibd.longest: a header line, then per individual, region and threshold "ind chr first_pos
+// last_pos n_sites min_len p_any p_none" (tab-separated, ordered by individual, then region, then
+// threshold; IDs, chromosome names, positions and regions as --ibd_by_length writes them, with
+// --longest_window for the windows): the probability that some IBD run of the region is of at
+// least min_len (Mb, or sites with --longest_sites) and the probability that none is.  Doubles as
+// %.10g; everything conditional on the final indF, alpha and frequencies.
+void write_ibd_longest(const Params& P, Cohort& C) {
+  if (!nghmm_chain_ibd_longest)
+    fatal(__FUNCTION__, "--ibd_longest: the library has no nghmm_chain_ibd_longest!");
+  const uint64_t I = P.n_ind, S = P.n_sites, K = P.longest.size();
+  std::vector<uint64_t> begin, end;
+  std::vector<size_t> chrom;   // the chromosome run of every region
+  for (size_t c = 0; c < P.chrom_first.size(); c++) {
+    const uint64_t a = P.chrom_first[c], b = c + 1 < P.chrom_first.size() ? P.chrom_first[c + 1] : S;
+    const uint64_t w = P.longest_window ? P.longest_window : b - a;
+    for (uint64_t lo = a; lo < b; lo += w) {
+      begin.push_back(lo);
+      end.push_back(b - lo < w ? b : lo + w);
+      chrom.push_back(c);
+    }
+  }
+  const uint64_t R = begin.size();
+  std::vector<nghmm_longest_stat> st((size_t)I * R * K);
+  check(nghmm_chain_ibd_longest(C.hs.data(), C.n(), P.longest_sites ? 0 : NGHMM_LONGEST_MB, (uint32_t)K,
+                                P.longest.data(), R, begin.data(), end.data(), st.data()),
+        "ibd_longest");
+  const std::string name = P.prefix + ".ibd.longest";
+  FILE* fh = fopen(name.c_str(), "w");
+  if (!fh) fatal(__FUNCTION__, "cannot open longest-tract output file!");
+  setvbuf(fh, nullptr, _IOFBF, 1 << 22);
+  fputs("ind\tchr\tfirst_pos\tlast_pos\tn_sites\tmin_len\tp_any\tp_none\n", fh);
+  for (uint64_t i = 0; i < I; i++) {
+    const std::string id = P.ind_names.empty() ? "ind" + std::to_string(i) : P.ind_names[i];
+    for (uint64_t r = 0; r < R; r++)
+      for (uint64_t k = 0; k < K; k++) {
+        const nghmm_longest_stat& t = st[(i * R + r) * K + k];
+        fprintf(fh, "%s\t%s\t%llu\t%llu\t%llu\t%.10g\t%.10g\t%.10g\n", id.c_str(),
+                P.chrom_name[chrom[r]].c_str(), (unsigned long long)P.site_pos[begin[r]],
+                (unsigned long long)P.site_pos[end[r] - 1], (unsigned long long)(end[r] - begin[r]),
+                P.longest[k], t.p_any, t.p_none);
+      }
+  }
+  if (fclose(fh) != 0) fatal(__FUNCTION__, "cannot write the longest-tract output file!");
+}
+
 // PREFIX.ibd.sharing: a header line, then per pair of individuals i <= j, in (i, j) order,
 // "IND_ID1 IND_ID2 vit_both post_both post_prod" (tab-separated; IDs as --ibd_bed names them): the
 // sites, genome-wide, at which both are IBD in the decoded path, at which both posteriors reach
@@ -2050,6 +2108,8 @@ void parse_cmd_args(Params& P, int argc, char** argv) {  // parse_args.cpp:41-22
       {"ibd_moments", no_argument, nullptr, 1032},    {"moments_window", required_argument, nullptr, 1033},
       {"ibd_by_length", required_argument, nullptr, 1034}, {"by_length_sites", no_argument, nullptr, 1035},
       {"by_length_window", required_argument, nullptr, 1036},
+      {"ibd_longest", required_argument, nullptr, 1037}, {"longest_sites", no_argument, nullptr, 1038},
+      {"longest_window", required_argument, nullptr, 1039},
       {0, 0, 0, 0}};
   long taus_kat = 0;
   bool parse_kat = false, se_kat = false;
@@ -2136,6 +2196,26 @@ void parse_cmd_args(Params& P, int argc, char** argv) {  // parse_args.cpp:41-22
       case 1036:
         if (atoll(optarg) < 1) fatal(__FUNCTION__, "invalid --by_length_window (sites per window)!");
         P.by_length_window = strtoull(optarg, nullptr, 10);
+        break;
+      case 1037: {   // L1,L2,...: every field a number; the rest is checked once the unit is known
+        P.ibd_longest = true;
+        P.longest.clear();
+        const char* q = optarg;
+        while (true) {
+          char* e = nullptr;
+          const double v = strtod(q, &e);
+          if (e == q || (*e != ',' && *e != '\0'))
+            fatal(__FUNCTION__, "invalid --ibd_longest (a comma-separated list of minimum lengths)!");
+          P.longest.push_back(v);
+          if (*e == '\0') break;
+          q = e + 1;
+        }
+        break;
+      }
+      case 1038: P.longest_sites = true; break;
+      case 1039:
+        if (atoll(optarg) < 1) fatal(__FUNCTION__, "invalid --longest_window (sites per window)!");
+        P.longest_window = strtoull(optarg, nullptr, 10);
         break;
       case 1026: {   // a,b,...: every field a number in [0, 1]
         P.freq_levels.clear();
@@ -2290,6 +2370,23 @@ void parse_cmd_args(Params& P, int argc, char** argv) {  // parse_args.cpp:41-22
   }
   if (!P.ibd_by_length && (P.by_length_window || P.by_length_sites))
     warn(__FUNCTION__, "--by_length_window and --by_length_sites are only used by --ibd_by_length");
+  if (P.ibd_longest) {
+    if (!nghmm_chain_ibd_longest)
+      fatal(__FUNCTION__, "--ibd_longest: the library has no nghmm_chain_ibd_longest!");
+    if (P.longest.empty() || P.longest.size() > 8)
+      fatal(__FUNCTION__, "invalid --ibd_longest (1 to 8 minimum lengths)!");
+    for (size_t k = 0; k < P.longest.size(); k++) {
+      const double v = P.longest[k];
+      const bool ok = std::isfinite(v) && (P.longest_sites ? (v >= 1 && v == std::floor(v)) : v >= 0) &&
+                      (k == 0 || v > P.longest[k - 1]);
+      if (!ok)
+        fatal(__FUNCTION__, P.longest_sites
+                                ? "invalid --ibd_longest (strictly increasing whole numbers of sites >= 1)!"
+                                : "invalid --ibd_longest (strictly increasing lengths in Mb >= 0)!");
+    }
+  }
+  if (!P.ibd_longest && (P.longest_window || P.longest_sites))
+    warn(__FUNCTION__, "--longest_window and --longest_sites are only used by --ibd_longest");
   if (P.min_iters < 1 || P.max_iters < 1 || P.min_iters >= P.max_iters)
     fatal(__FUNCTION__, "invalid number of iterations!");
   if (P.n_threads < 1) fatal(__FUNCTION__, "invalid number of threads!");
@@ -2322,8 +2419,9 @@ void parse_cmd_args(Params& P, int argc, char** argv) {  // parse_args.cpp:41-22
     if (P.ind_names.size() != P.n_ind)
       fatal(__FUNCTION__, "number of lines in --ind_names file is not --n_ind!");
     if (!P.ibd_bed && !P.sample_paths && !P.indF_se && !P.ibd_summary && !P.ibd_sharing && !P.ibd_support &&
-        !P.ibd_bounds && !P.geno_summary && !P.ibd_expect && !P.ibd_moments && !P.ibd_by_length)
-      warn(__FUNCTION__, "--ind_names is only used by --ibd_bed, --sample_paths, --indF_se, --ibd_summary, --ibd_sharing, --ibd_support, --ibd_bounds, --geno_summary, --ibd_expect, --ibd_moments and --ibd_by_length");
+        !P.ibd_bounds && !P.geno_summary && !P.ibd_expect && !P.ibd_moments && !P.ibd_by_length &&
+        !P.ibd_longest)
+      warn(__FUNCTION__, "--ind_names is only used by --ibd_bed, --sample_paths, --indF_se, --ibd_summary, --ibd_sharing, --ibd_support, --ibd_bounds, --geno_summary, --ibd_expect, --ibd_moments, --ibd_by_length and --ibd_longest");
   }
   P.prefix = P.out_prefix;
 }
@@ -2427,6 +2525,7 @@ void finish_run(Params& P, Cohort& C) {
   if (P.ibd_expect) write_ibd_expect(P, C);
   if (P.ibd_moments) write_ibd_moments(P, C);
   if (P.ibd_by_length) write_ibd_by_length(P, C);
+  if (P.ibd_longest) write_ibd_longest(P, C);
   if (P.verbose >= 2)  // (not a line of the reference's)
     fprintf(P.out, "> decoded in %.2f s, output files written in %.2f s\n", t1 - t0, omp_get_wtime() - t1);
 }
@@ -2550,6 +2649,7 @@ int main(int argc, char** argv) {
         runs[r].ibd_expect = P.ibd_expect && r == best;
         runs[r].ibd_moments = P.ibd_moments && r == best;
         runs[r].ibd_by_length = P.ibd_by_length && r == best;
+        runs[r].ibd_longest = P.ibd_longest && r == best;
         finish_run(runs[r], cs[r]);
       }
       fclose(runs[r].out);
@@ -2581,6 +2681,7 @@ int main(int argc, char** argv) {
       }
       if (P.ibd_moments) exts.push_back(".ibd.moments");
       if (P.ibd_by_length) exts.push_back(".ibd.bylength");
+      if (P.ibd_longest) exts.push_back(".ibd.longest");
       for (unsigned k = 1; P.sample_paths && k <= P.sample_keep; k++) {
         char tag[32];
         snprintf(tag, sizeof tag, ".sample_%02u.ibd", k);

@@ -174,6 +174,9 @@ def load_library():
         "nghmm_chain_ibd_by_length": (i32, [C.POINTER(vp), i32, i32, u32, dp, u64, C.POINTER(u64),
                                             C.POINTER(u64), vp]),
         "nghmm_debug_bylength_qmax": (i32, [vp, dp]),
+        "nghmm_ibd_longest": (i32, [vp, i32, u32, dp, u64, C.POINTER(u64), C.POINTER(u64), vp]),
+        "nghmm_chain_ibd_longest": (i32, [C.POINTER(vp), i32, i32, u32, dp, u64, C.POINTER(u64),
+                                          C.POINTER(u64), vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -221,6 +224,7 @@ EXPORTED_SYMBOLS = [
     "nghmm_ibd_expect", "nghmm_chain_ibd_expect",
     "nghmm_ibd_moments", "nghmm_chain_ibd_moments",
     "nghmm_ibd_by_length", "nghmm_chain_ibd_by_length", "nghmm_debug_bylength_qmax",
+    "nghmm_ibd_longest", "nghmm_chain_ibd_longest",
 ]
 
 OBJECTIVE_FN = C.CFUNCTYPE(C.c_double, C.c_uint32, C.c_double, C.c_double, C.c_void_p)
@@ -743,13 +747,16 @@ BYLENGTH_DTYPE = np.dtype([(n, np.float64) for n, _ in ByLengthStat._fields_])
 assert BYLENGTH_DTYPE.itemsize == C.sizeof(ByLengthStat) == 16
 
 
-def _ibd_by_length(call, check, n_ind, n_sites, min_len, unit, regions):
+def _ibd_by_length(call, check, n_ind, n_sites, min_len, unit, regions, dtype=None,
+                   name="ibd_by_length", mb_flag=None):
+    """What ibd_by_length and ibd_longest share: the checks of unit, thresholds and regions, the
+    record array [I][R][K] of `dtype` and the call; mb_flag is the entry's own bit for Mb."""
     u64p = C.POINTER(C.c_uint64)
     if unit not in ("sites", "mb"):
-        raise NgsFHMMError(-10, "ibd_by_length: unit is 'sites' or 'mb'")
+        raise NgsFHMMError(-10, f"{name}: unit is 'sites' or 'mb'")
     L = np.ascontiguousarray(np.atleast_1d(np.asarray(min_len, dtype=np.float64)))
     if L.ndim != 1:
-        raise NgsFHMMError(-10, "ibd_by_length: min_len is a number or a list of numbers")
+        raise NgsFHMMError(-10, f"{name}: min_len is a number or a list of numbers")
     if regions is None:
         reg = np.array([[0, n_sites]], dtype=np.uint64)
     else:
@@ -758,13 +765,14 @@ def _ibd_by_length(call, check, n_ind, n_sites, min_len, unit, regions):
             reg = reg.reshape(0, 2)
         if reg.ndim != 2 or reg.shape[1] != 2 or not np.issubdtype(reg.dtype, np.integer) or \
                 (reg < 0).any():
-            raise NgsFHMMError(-10, "ibd_by_length: regions is an [R][2] array of site indices "
+            raise NgsFHMMError(-10, f"{name}: regions is an [R][2] array of site indices "
                                     "(begin, end)")
         reg = reg.astype(np.uint64)
     R, K = len(reg), len(L)
     begin, end = np.ascontiguousarray(reg[:, 0]), np.ascontiguousarray(reg[:, 1])
-    stats = np.zeros((n_ind, R, K), dtype=BYLENGTH_DTYPE)
-    check(call(BYLENGTH_MB if unit == "mb" else 0, K, _dp(L) if K else None, R,
+    stats = np.zeros((n_ind, R, K), dtype=BYLENGTH_DTYPE if dtype is None else dtype)
+    mb_flag = BYLENGTH_MB if mb_flag is None else mb_flag
+    check(call(mb_flag if unit == "mb" else 0, K, _dp(L) if K else None, R,
                begin.ctypes.data_as(u64p) if R else None, end.ctypes.data_as(u64p) if R else None,
                C.c_void_p(stats.ctypes.data) if R and K else None))
     return stats
@@ -782,6 +790,30 @@ def by_length_classes(stats):
     mean = np.full(ct.shape, np.nan)
     np.divide(cl, ct, out=mean, where=ct != 0)
     return {"tracts": ct, "length": cl, "mean_length": mean}
+
+
+LONGEST_MB = 1         # nghmm_ibd_longest: thresholds in Mb instead of sites
+
+
+class LongestStat(C.Structure):      # nghmm_longest_stat (include/nghmm.h)
+    _fields_ = [(n, C.c_double) for n in ("p_any", "p_none")]
+
+
+LONGEST_DTYPE = np.dtype([(n, np.float64) for n, _ in LongestStat._fields_])
+assert LONGEST_DTYPE.itemsize == C.sizeof(LongestStat) == 16
+
+
+def longest_classes(stats):
+    """ibd_longest's records [..][K] as the distribution of the longest run: a float array
+    [..][K + 1] -- class 0: the longest run is below L_1 (p_none of the first threshold, which
+    includes no run at all), class k: it lies in [L_k, L_{k+1}) (a difference of p_any), class K:
+    it is at least L_K.  The classes add up to 1 to the accuracy of p_any + p_none."""
+    pa = np.asarray(stats["p_any"], dtype=np.float64)
+    out = np.empty(pa.shape[:-1] + (pa.shape[-1] + 1,))
+    out[..., 0] = np.asarray(stats["p_none"], dtype=np.float64)[..., 0]
+    out[..., 1:-1] = pa[..., :-1] - pa[..., 1:]
+    out[..., -1] = pa[..., -1]
+    return out
 
 
 SHARING_VITERBI = 1    # nghmm_ibd_sharing sources, a bit mask (include/nghmm.h)
@@ -1345,6 +1377,16 @@ class NgsFHMM:
         return _ibd_by_length(lambda *a: self.lib.nghmm_ibd_by_length(self._h, *a), self._check,
                               self.n_ind, self.n_sites, min_len, unit, regions)
 
+    def ibd_longest(self, min_len, unit="sites", regions=None):
+        """The distribution of the longest IBD run, exactly (nghmm_ibd_longest): [I][R][K] of
+        LONGEST_DTYPE -- p_any, the probability that some IBD run of the region is of at least
+        min_len[k], and p_none, that none is (from its own sum).  min_len, unit and regions as
+        ibd_by_length takes them; a run is cut at chromosome starts and at the region's edges.
+        longest_classes turns the records into the classes of the longest run."""
+        return _ibd_by_length(lambda *a: self.lib.nghmm_ibd_longest(self._h, *a), self._check,
+                              self.n_ind, self.n_sites, min_len, unit, regions, LONGEST_DTYPE,
+                              "ibd_longest", LONGEST_MB)
+
     def by_length_qmax(self):
         """The largest |Q| the last ibd_by_length met (nghmm_debug_bylength_qmax): times 2^-53 the
         absolute error in the exponent of a window's probability."""
@@ -1554,6 +1596,16 @@ class Chain:
         return _ibd_by_length(
             lambda *a: self.lib.nghmm_chain_ibd_by_length(self._arr, len(self.handles), *a),
             self.handles[0]._check, self.n_ind, self.n_sites, min_len, unit, regions)
+
+    def ibd_longest(self, min_len, unit="sites", regions=None):
+        """NgsFHMM.ibd_longest over the chain (nghmm_chain_ibd_longest): global site indices; the
+        lane state crosses the cuts, so the records are the single handle's bytes and a threshold
+        may reach past any number of shards."""
+        self._members_open()
+        return _ibd_by_length(
+            lambda *a: self.lib.nghmm_chain_ibd_longest(self._arr, len(self.handles), *a),
+            self.handles[0]._check, self.n_ind, self.n_sites, min_len, unit, regions, LONGEST_DTYPE,
+            "ibd_longest", LONGEST_MB)
 
     def ibd_sharing(self, what=("viterbi", "posterior"), threshold=0.5, site_begin=0, site_end=None):
         """NgsFHMM.ibd_sharing over the chain (nghmm_chain_ibd_sharing): global site indices, the

@@ -1,0 +1,67 @@
+// nghmm_longest_stub.cpp -- the longest-tract entries of include/nghmm.h for the CPU stand-in
+// tests/stub/nghmm_stub.cpp, TEST INFRASTRUCTURE ONLY (linked next to it by
+// tests/test_longest_cpu.py).  The records are formulas of (individual, region, threshold, unit),
+// restated in that test, so that the host's --ibd_longest writer can be checked byte for byte.
+// Nothing here is a fallback.
+#include <cmath>
+#include <cstdint>
+#include <string>
+#include <vector>
+
+#include "../../include/nghmm.h"
+
+// the stand-in's handle, token for token as tests/stub/nghmm_stub.cpp defines it
+struct nghmm_handle {
+  uint64_t I, S;
+  int mode;
+  bool packed, loading = false, loaded = false;
+  std::vector<double> indF, alpha, freq, pos;
+  std::vector<uint8_t> seen;  // per site: loaded exactly once
+  nghmm_handle* parent = nullptr;
+  int replicas = 0, g_n = 0;
+  uint64_t checksum = 0;
+};
+
+extern "C" {
+
+int nghmm_chain_ibd_longest(nghmm_t** hs, int n, int what, uint32_t n_lengths, const double* min_length,
+                              uint64_t n_regions, const uint64_t* region_begin, const uint64_t* region_end,
+                              nghmm_longest_stat* stats) {
+  if (!hs || n < 1 || !hs[0] || (n > 1 && hs[0]->g_n != n)) return NGHMM_ERR_ARG;
+  if (what & ~NGHMM_LONGEST_MB) return NGHMM_ERR_ARG;
+  if (n_lengths < 1 || n_lengths > 8 || !min_length) return NGHMM_ERR_ARG;
+  if (n_regions == 0 || !stats || !region_begin || !region_end) return NGHMM_ERR_ARG;
+  const bool mb = (what & NGHMM_LONGEST_MB) != 0;
+  for (uint32_t k = 0; k < n_lengths; ++k) {
+    const double L = min_length[k];
+    if (!std::isfinite(L) || (mb ? L < 0 : (L < 1 || L != std::floor(L))) || (k > 0 && !(L > min_length[k - 1])))
+      return NGHMM_ERR_ARG;
+  }
+  const uint64_t I = hs[0]->I;
+  uint64_t S = 0;
+  for (int r = 0; r < n; ++r) {
+    if (!hs[r] || !hs[r]->loaded || hs[r]->I != I) return NGHMM_ERR_ARG;
+    S += hs[r]->S;
+  }
+  for (uint64_t r = 0; r < n_regions; ++r)
+    if (!(region_begin[r] < region_end[r]) || region_end[r] > S ||
+        (r > 0 && region_begin[r] < region_end[r - 1]))
+      return NGHMM_ERR_ARG;
+  for (uint64_t i = 0; i < I; ++i)
+    for (uint64_t r = 0; r < n_regions; ++r)
+      for (uint32_t k = 0; k < n_lengths; ++k) {
+        const double a = (double)region_begin[r], len = (double)(region_end[r] - region_begin[r]);
+        nghmm_longest_stat t;
+        t.p_any = (1.0 + (double)i) / ((2.0 + (double)i + a) * (1.0 + min_length[k]));
+        t.p_none = (mb ? 0.5 : 0.25) / (double)(k + 1) + 1e-7 * len + 1e-9 * (double)i;
+        stats[(i * n_regions + r) * n_lengths + k] = t;   // (writes every record the caller made room for)
+      }
+  return NGHMM_OK;
+}
+
+int nghmm_ibd_longest(nghmm_t* h, int what, uint32_t n_lengths, const double* min_length, uint64_t n_regions,
+                        const uint64_t* region_begin, const uint64_t* region_end, nghmm_longest_stat* stats) {
+  return nghmm_chain_ibd_longest(&h, 1, what, n_lengths, min_length, n_regions, region_begin, region_end, stats);
+}
+
+}  // extern "C"
