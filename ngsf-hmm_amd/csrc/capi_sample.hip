@@ -102,7 +102,13 @@ int sample_impl(nghmm_t** hs, int n, uint64_t seed, uint32_t n_draws, nghmm_path
       HIP_TRY(hipGetLastError());
       HIP_TRY(hipMemcpyAsync(x.seg.data(), x.scr.seg, (size_t)nd * I * sizeof(SampleSeg),
                              hipMemcpyDeviceToHost, h->stream));
-      if (np)
+      if (np && x.scr.pitch == h->S && S_tot == h->S)
+        // one handle in exact mode: the rows follow each other on both sides, one plain copy (the
+        // strided one to pageable memory makes the runtime keep staging memory of its own, 2 MiB
+        // at a time, when a second stream of the process has done it too)
+        HIP_TRY(hipMemcpyAsync(paths + (size_t)draw0 * I * S_tot, x.scr.paths, (size_t)np * I * h->S,
+                               hipMemcpyDeviceToHost, h->stream));
+      else if (np)
         HIP_TRY(hipMemcpy2DAsync(paths + (size_t)draw0 * I * S_tot + x.base, S_tot, x.scr.paths,
                                  x.scr.pitch, h->S, (size_t)np * I, hipMemcpyDeviceToHost, h->stream));
       HIP_TRY(sync_stream(h));
