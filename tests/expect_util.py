@@ -333,7 +333,9 @@ def sampler_check(stats, exact):
 
 
 # The lane length the spread is measured with: what NgsFHMM.layout() reports for the 20 x 5003
-# cohort of support_util.gpu_cohort (the region sets only use it to place single-site regions).
+# cohort of support_util.gpu_cohort with ONE wave per individual (NGHMM_FAST_C=1; by itself the
+# cohort gets 5 waves and lanes of 16 sites, tests/test_gpu_layouts.py prints both).  The region
+# sets only use it to place single-site regions, and exact mode's tests fall back on it.
 SPREAD_LANE_SITES = 80
 # The spread of the two yardsticks on support_util.gpu_cohort, largest |A - B| per field over all
 # the region sets of region_sets(5003, pos, 80) and over the site records, with the decoded path

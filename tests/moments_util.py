@@ -220,7 +220,7 @@ def confident_case(pkg):
 
 
 # The lane length the spread is measured with (expect_util.SPREAD_LANE_SITES: what
-# NgsFHMM.layout() reports for the 20 x 5003 cohort).
+# NgsFHMM.layout() reports for the 20 x 5003 cohort with one wave per individual).
 SPREAD_LANE_SITES = xu.SPREAD_LANE_SITES
 # The spread of the two yardsticks, largest |A - B| per length and field, (1) on
 # support_util.gpu_cohort over all the region sets of expect_util.region_sets(5003, pos, 80) and

@@ -4,7 +4,8 @@ with arguments that reach its own scratch and code paths, as an ordered dict of 
 nghmm_create_replica promises that every call on a replica behaves exactly as on an independent
 handle loaded with the same data, so two batteries are compared with ==, key by key: there is no
 tolerance (both modes are deterministic; post_prod's split plan is a function of
-(I, site_begin, site_end) alone).
+(I, site_begin, site_end) alone).  The layout tests (tests/test_gpu_layouts.py) ask for the same
+battery as arrays and compare two handles of different lane layouts by tests/layout_util.RULES.
 
 COVERED is the set of C entry points the battery reaches; tests/test_replica_battery_cpu.py holds it
 against include/nghmm.h, so that an entry point added without a replica test fails there."""
@@ -36,8 +37,14 @@ COVERED = frozenset({
 REGION_SETS = {"fast": ("whole", "chrom", "gaps", "edges"), "exact": ("gaps",)}
 # a site range off the 64-site step of the sharing kernels
 SHARING_RANGE = (37, 4001)
+
 # the only key that is the data itself: equal whatever the start
 DATA_KEYS = ("gl",)
+
+
+def sharing_range(n_sites):
+    """SHARING_RANGE, cut to data of fewer sites (an odd end still)."""
+    return SHARING_RANGE[0], min(SHARING_RANGE[1], n_sites - 5)
 
 
 def cohort_regions(pkg, cohort, mode_name, lane_sites):
@@ -80,8 +87,13 @@ def reset(h, start):
     h.init_emission()
 
 
+class _Arrays(collections.OrderedDict):
+    """A battery that keeps every record as a copy of the array itself (text stays bytes)."""
+
+
 def _records(out, name, rec):
-    """A structured array, or a tuple / dict of arrays some of which may be None, as bytes."""
+    """A structured array, or a tuple / dict of arrays some of which may be None, as bytes (into an
+    _Arrays: as arrays)."""
     if isinstance(rec, dict):
         for k, v in rec.items():
             _records(out, f"{name}.{k}", v)
@@ -89,16 +101,44 @@ def _records(out, name, rec):
         for k, v in enumerate(rec):
             _records(out, f"{name}.{k}", v)
     elif rec is not None:
-        out[name] = rec if isinstance(rec, bytes) else np.ascontiguousarray(rec).tobytes()
+        if isinstance(rec, bytes):
+            out[name] = rec
+        elif isinstance(out, _Arrays):
+            out[name] = np.array(rec, copy=True)
+        else:
+            out[name] = np.ascontiguousarray(rec).tobytes()
 
 
-def battery(pkg, h, regions):
+def lkl_points(n_ind):
+    """(ind, F, alpha) of the battery's lkl call: 2 I points."""
+    n = 2 * n_ind
+    return np.arange(n) % n_ind, np.linspace(0.05, 0.9, n), np.geomspace(1e-3, 3.0, n)
+
+
+def posterior_part(n_ind):
+    """(first individual, number) of the battery's partial format_posteriors call."""
+    return min(3, n_ind - 1), max(n_ind // 4, 1)
+
+
+def info_points(n_ind):
+    """(F, alpha) of the battery's obs_info call at given points."""
+    return np.linspace(0.1, 0.8, n_ind), np.geomspace(0.01, 2.0, n_ind)
+
+
+def battery(pkg, h, regions, arrays=False, estep_only=False, ranges=None):
     """On a handle that has parameters and emissions: iter_EM once, viterbi, then every output.
     regions: {name: [R][2]}; the per-cell outputs of geno_smooth and the site records are asked for
-    with the first set only.  Returns an ordered dict of name -> bytes."""
-    out = collections.OrderedDict()
+    with the first set only.  Returns an ordered dict of name -> bytes.
+    arrays: name -> array instead (tests/layout_util.py compares within tolerances).
+    estep_only: estep() in place of iter_EM() and no frequency step at the end, so that the
+    parameters stay what the caller set (the L-BFGS-B M-step amplifies last-bit differences).
+    ranges: hand-made records [n][3] for tract_support / tract_bounds besides the decode's tracts."""
+    out = _Arrays() if arrays else collections.OrderedDict()
     I, S = h.n_ind, h.n_sites
-    h.iter_EM()
+    if estep_only:
+        h.estep()
+    else:
+        h.iter_EM()
     path = h.viterbi()
     _records(out, "indF", h.indF)
     _records(out, "alpha", h.alpha)
@@ -111,9 +151,8 @@ def battery(pkg, h, regions):
     _records(out, "geno_posteriors", h.geno_posteriors())
     _records(out, "geno_posteriors.chunk", h.geno_posteriors(S // 5 + 1, S // 7))
     _records(out, "format_posteriors", h.format_posteriors())
-    _records(out, "format_posteriors.part", h.format_posteriors(3, I // 4))
-    n = 2 * I
-    _records(out, "lkl", h.lkl(np.arange(n) % I, np.linspace(0.05, 0.9, n), np.geomspace(1e-3, 3.0, n)))
+    _records(out, "format_posteriors.part", h.format_posteriors(*posterior_part(I)))
+    _records(out, "lkl", h.lkl(*lkl_points(I)))
 
     tv = h.ibd_tracts("viterbi")
     _records(out, "ibd_tracts.viterbi", tv)
@@ -121,9 +160,12 @@ def battery(pkg, h, regions):
     _records(out, "sample_paths", h.sample_paths(3, seed=5, keep=2))
     _records(out, "tract_support", h.tract_support(tv))
     _records(out, "tract_bounds", h.tract_bounds(tv))
+    if ranges is not None:
+        _records(out, "tract_support.hand", h.tract_support(ranges))
+        _records(out, "tract_bounds.hand", h.tract_bounds(ranges))
     _records(out, "freq_info", h.freq_info(fu.LEVELS, cavity=True))
     _records(out, "obs_info", h.obs_info())
-    _records(out, "obs_info.at", h.obs_info(np.linspace(0.1, 0.8, I), np.geomspace(0.01, 2.0, I)))
+    _records(out, "obs_info.at", h.obs_info(*info_points(I)))
     first = True
     for tag, reg in regions.items():
         _records(out, f"geno_smooth.{tag}", h.geno_smooth(reg, sites=first, post=first, call=first))
@@ -136,7 +178,9 @@ def battery(pkg, h, regions):
             _records(out, f"ibd_longest.{u}.{tag}", h.ibd_longest(L, unit=u, regions=reg))
         first = False
     _records(out, "ibd_sharing", h.ibd_sharing(("viterbi", "posterior")))
-    _records(out, "ibd_sharing.range", h.ibd_sharing(("viterbi", "posterior"), 0.7, *SHARING_RANGE))
+    _records(out, "ibd_sharing.range", h.ibd_sharing(("viterbi", "posterior"), 0.7, *sharing_range(S)))
+    if estep_only:
+        return out
     # the frequency step on its own (it has a chain twin): from the posteriors of the iteration above
     h.mstep_freq(1)
     _records(out, "mstep_freq.freq", h.freq)

@@ -182,13 +182,14 @@ def enumerate_support(eprob, pos, F, alpha, tracts):
     return out, post
 
 
-def gpu_cohort(pkg):
+def gpu_cohort(pkg, n_ind=20, n_sites=5003):
     """The cohort of tests/test_gpu_support.py, shared with the yardstick-spread measurement of
     tests/test_support_cpu.py: 20 x 5003 (ragged against every block size), three chromosomes,
     missing cells, random indF; alpha = 1e-3 for the first five individuals (tracts that span many
-    lane-chunks), random for the rest; one frequency.
+    lane-chunks), random for the rest; one frequency.  (n_ind, n_sites: the same recipe at another
+    size, for tests/test_gpu_layouts.py.)
     Returns (simulated data, normalised log likelihoods, indF, alpha, freq)."""
-    I, S = 20, 5003
+    I, S = n_ind, n_sites
     d = pkg.simulate.simulate(I, S, seed=41, n_chrom=3, indF="r", alpha="r", missing_rate=0.03)
     rng = np.random.default_rng(42)
     F, A = rng.uniform(0.02, 0.95, I), rng.uniform(0.01, 2.0, I)

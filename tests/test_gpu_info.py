@@ -14,6 +14,7 @@ import pytest
 import cli_util
 import info_util as iu
 from conftest import has_gpu
+from layout_util import forced_layout
 
 pytestmark = [pytest.mark.gpu, pytest.mark.skipif(not has_gpu(), reason="needs an MI355X")]
 
@@ -27,12 +28,8 @@ def _data(pkg, n_ind, n_sites, seed):
 
 def _handle(pkg, d, pos, F, A, mode, packed=False, iters=2, fast_c=None):
     m = (pkg.MODE_FAST if mode == "fast" else pkg.MODE_EXACT) | (pkg.GENO_PACKED if packed else 0)
-    if fast_c:
-        os.environ["NGHMM_FAST_C"] = str(fast_c)
-    try:
+    with forced_layout(fast_c):
         h = pkg.NgsFHMM(d.n_ind, d.n_sites, mode=m)
-    finally:
-        os.environ.pop("NGHMM_FAST_C", None)
     if packed:
         h.load_raw(d.gl, pos, space=0, call_geno=True)
     else:
