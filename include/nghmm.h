@@ -1142,6 +1142,90 @@ int nghmm_chain_ibd_longest(nghmm_t** hs, int n_handles, int what, uint32_t n_le
                             const double* min_length, uint64_t n_regions, const uint64_t* region_begin,
                             const uint64_t* region_end, nghmm_longest_stat* stats);
 
+/* ---- per-site posterior of lying in a long IBD tract ----
+ * Per individual, site and threshold L_k the probability P_k(s) that site s lies in an IBD tract
+ * of length >= L_k, exactly, at the handle's CURRENT indF, alpha and freq: the track "this site
+ * lies in a ROH above 1 Mb".  Everything is nghmm_ibd_by_length's unless stated: tracts (runs of
+ * z = 1 cut at chromosome starts), len(a, b), cum_s, d_s, sigma_a, rho_s, blocked steps, W(a, b),
+ * the thresholds (1 <= K <= 8, strictly increasing; whole numbers of sites >= 1, or with
+ * NGHMM_LONG_MB finite and >= 0 Mb) and the table b_k(a).  pi_s = P(z_s = 1 | y), unsnapped.
+ * Per threshold k and site s, with c0 the first site of s's chromosome:
+ *   lo_k(s) = the largest a <= s in s's chromosome with len(a, s) >= L_k, or none; non-decreasing
+ *             in s inside a chromosome, a host table like b_k (one two-pointer pass, the
+ *             comparison that forms b_k, so that a <= lo_k(s) iff b_k(a) <= s)
+ *   T_k(a)  = sigma_a W(a, b_k(a)), 0 where b_k(a) is none: nghmm_ibd_by_length's tracts term
+ *   A_k(s)  = pi_lo W(lo, s) with lo = lo_k(s), 0 if there is none: the paths that are IBD on the
+ *             whole minimal window that ends at s
+ *   B_k(s)  = the sum of T_k(a) over a = lo + 1 .. s (a = c0 .. s if lo is none): the runs that
+ *             begin too late to be long at s but get there
+ *   P_k(s)  = A_k(s) + B_k(s)
+ * 0 <= P_k(s) <= pi_s; P_k is non-increasing in k; at L = 1 site and at 0 Mb P = pi, bit for bit;
+ * a state the data exclude and a threshold no chromosome reaches give exactly 0; nothing is NaN.
+ * P_k(s) - T_k(s) = P(s - 1 and s lie in the same tract of length >= L_k | y).
+ *
+ * Outputs, each optional (NULL skips it; not all three); no output's bits depend on which others
+ * are asked for, or on which other regions are:
+ *   post [K][I][S_tot]  P_k, each plane in the layout of nghmm_get_posteriors' IBD state
+ *   site_stats [S_tot][K]  sum = sum_i P_k(s), the individuals added in index order; count = the
+ *             individuals with P_k(s) >= threshold (in [0, 1], as nghmm_ibd_summary's)
+ *   region_stats [I][n_regions][K], nghmm_ibd_summary's regions:
+ *             sites = sum over the region's sites of P_k(s)
+ *             mb    = sum over its sites that are no chromosome start of d_s max(P_k(s) - T_k(s), 0)
+ *             Every site contributes its own term (not the tract's whole length to the region it
+ *             begins in), so regions that partition the data add up; both fields are filled
+ *             whichever unit the thresholds are in.  Over whole chromosomes sites is
+ *             nghmm_ibd_by_length's length with thresholds in sites and mb its length with
+ *             thresholds in Mb; at L = 1 site sites is nghmm_ibd_expect's ibd and at 0 Mb mb its
+ *             ibd_mb, on any region.
+ *
+ * Orders (no float atomics; the same arguments give the same bits on every call).  The cells
+ * sigma_s, Q_s, n_s are nghmm_ibd_by_length's, in its orders, and pi_s = xi_s(0, 1) + xi_s(1, 1)
+ * comes from the same walk.  T_k(a) = sigma_a (n_b == n_a ? exp(Q_b - Q_a) : 0) at b = b_k(a).  A
+ * term T_k(a) with a blocked step in (a, s] is exactly 0 when its window reaches beyond s, so
+ * B_k is a difference of the prefix U of T_k that restarts at every blocked step (where Q does):
+ *   n_lo == n_s:  P = pi_lo exp(Q_s - Q_lo) + max(U_s - U_lo, 0);   otherwise (and without lo)  P = U_s;
+ *   then P = min(P, pi_s), so that 0 <= P <= pi and P = 0 where pi = 0 hold exactly.
+ * U in fast mode (a lane-chunk is T consecutive sites of nghmm_fast_layout): within a lane-chunk
+ * T_k is added in site order from 0, restarting at a blocked step; what enters a lane-chunk is
+ * the sum of the lane-chunks in front of it back to the last blocked step, the 64 lane-chunks of
+ * a wave in a Hillis-Steele tree (steps 1, 2, .., 32) and the waves in site order; U_s = (what
+ * enters, if the lane-chunk has no blocked step up to s) + (the lane-chunk's own sum).  A
+ * region's sums: pieces at the lane-chunk edges, each added from its last site to its first, the
+ * pieces in site order, as nghmm_ibd_by_length.  Exact mode: one lane per individual, U in site
+ * order, a region's terms added to 0 from its last site to its first; exp through detmath.h.
+ *
+ * Accuracy: W as nghmm_ibd_by_length (2^-53 max|Q| in the exponent); the difference U_s - U_lo
+ * carries an absolute error of 2^-53 U, U being the expected number of long-tract starts since
+ * the last blocked step -- below W's own error.
+ *
+ * NGHMM_ERR_ARG with a message as nghmm_ibd_by_length, and for a threshold outside [0, 1] (NaN
+ * included) and for three NULL outputs; region_stats, region_begin and region_end are NULL iff
+ * n_regions == 0.  Self-contained and read-only exactly like nghmm_ibd_by_length: it refreshes stale
+ * emissions itself, and an EM iteration after the call gives the bits it would have given without
+ * it.  Device scratch, kept by the handle and allocated on first use (NGHMM_ERR_NOMEM when it
+ * cannot be had): nghmm_ibd_by_length's 36 bytes per cell (sigma, Q, n; pi in the place of D, T_k
+ * in the place of M) and 40 bytes per cell more (a packed 32-byte record pi, Q, U, n that the
+ * gather at lo_k(s) reads, and P_k), 8 more when post is asked for: one threshold is worked at a
+ * time, so nothing per cell grows with K; 84 bytes per (individual, lane-chunk); 8 n_lengths bytes
+ * per site for b_k and lo_k; 16 per (individual, piece), 16 n_lengths per (individual, region) and
+ * per site with site records.   */
+enum { NGHMM_LONG_MB = 1 };
+typedef struct nghmm_long_region_stat {  /* 16 bytes; one per (individual, region, threshold) */
+  double sites;  /* expected number of the region's sites in tracts of length >= L_k */
+  double mb;     /* expected Mb of the region inside such tracts */
+} nghmm_long_region_stat;
+typedef struct nghmm_long_site_stat {  /* 16 bytes; one per (site, threshold) */
+  double sum;      /* sum over the individuals of P_k(s) */
+  uint64_t count;  /* individuals with P_k(s) >= threshold */
+} nghmm_long_site_stat;
+#ifdef __cplusplus
+static_assert(sizeof(nghmm_long_region_stat) == 16 && sizeof(nghmm_long_site_stat) == 16, "record size");
+#endif
+int nghmm_ibd_long(nghmm_t* h, int what, uint32_t n_lengths, const double* min_length, double threshold,
+                   uint64_t n_regions, const uint64_t* region_begin, const uint64_t* region_end,
+                   nghmm_long_region_stat* region_stats, nghmm_long_site_stat* site_stats, double* post);
+/* include/nghmm_chain_long.h declares the same call over a chain of site shards. */
+
 /* ---- pairwise IBD sharing between individuals ----
  * How much IBD two individuals share over the sites [site_begin, site_end): three host matrices
  * [I][I], full and symmetric, reduced on the matrix cores from the decoded path and the

@@ -26,6 +26,7 @@ from .hmm import (NgsFHMM, NgsFHMMError, Group, Chain, MODE_EXACT, MODE_FAST, GE
                   EXPECT_VITERBI, EXPECT_REGION_DTYPE, EXPECT_SITE_DTYPE, expect_tract_length,
                   MOMENTS_MB, MOMENT_REGION_DTYPE, moment_sd,
                   BYLENGTH_MB, BYLENGTH_DTYPE, by_length_classes,
+                  LONG_MB, LONG_REGION_DTYPE, LONG_SITE_DTYPE, long_tracts,
                   LONGEST_MB, LONGEST_DTYPE, longest_classes)
 from . import simulate
 
@@ -40,4 +41,5 @@ __all__ = ["NgsFHMM", "NgsFHMMError", "Group", "Chain", "MODE_EXACT", "MODE_FAST
            "geno_em_freq", "het_outside_ibd", "EXPECT_VITERBI", "EXPECT_REGION_DTYPE",
            "EXPECT_SITE_DTYPE", "expect_tract_length", "MOMENTS_MB", "MOMENT_REGION_DTYPE",
            "moment_sd", "BYLENGTH_MB", "BYLENGTH_DTYPE", "by_length_classes",
+           "LONG_MB", "LONG_REGION_DTYPE", "LONG_SITE_DTYPE", "long_tracts",
            "LONGEST_MB", "LONGEST_DTYPE", "longest_classes"]

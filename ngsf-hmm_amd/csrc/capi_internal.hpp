@@ -140,6 +140,12 @@ struct nghmm_handle {
   DevScratch<uint8_t> d_lng;
   DevScratch<uint8_t> d_lng_cell;
   DevScratch<uint8_t> d_lng_ring;
+  // per-site posterior of lying in a long IBD tract (capi_long.hip): the regions, pieces and
+  // records, the lane-chunk scans, the b_k and lo_k tables, the boundary vectors and the halos; the
+  // packed records and P (40 bytes per cell, and 8 more when post is asked for); the cells
+  // themselves are d_byl_cell's
+  DevScratch<uint8_t> d_long;
+  DevScratch<uint8_t> d_long_cell;
   DevBuf<double> d_freq_new, d_hap;  // --freq_est 2 as intended: [S], [S][4]
 
   // multi-GPU shard

@@ -46,7 +46,12 @@
 // --ibd_longest L1,L2,... [--longest_sites] [--longest_window N] (PREFIX.ibd.longest: per
 // individual, chromosome or window of N sites and threshold the probability that some IBD run there
 // is of at least that length -- in Mb, or in sites with --longest_sites -- and that none is,
-// exactly, made on the device after the final decode).
+// exactly, made on the device after the final decode),
+// --ibd_long L1,L2,... [--long_sites] [--long_window N] [--long_thresh P] [--long_post]
+// (PREFIX.ibd.long.regions, PREFIX.ibd.long.sites and, with --long_post, PREFIX.ibd.long.post: per
+// site and threshold the posterior of lying in an IBD tract of at least that length -- in Mb, or
+// in sites with --long_sites -- summed per individual and chromosome or window of N sites, and per
+// site over the individuals, exactly, made on the device after the final decode).
 // --n_threads (the reference's pool size) sets the host threads used for input normalisation and output
 // formatting; results do not depend on it.
 #include <fcntl.h>
@@ -73,6 +78,7 @@
 #include <vector>
 
 #include "../../../include/nghmm.h"
+#include "../../../include/nghmm_chain_long.h"
 
 // referenced weakly: a build against a library without the tract entry still links, and
 // --ibd_bed then stops with a message
@@ -94,6 +100,8 @@
 #pragma weak nghmm_chain_ibd_by_length
 // ... and without the longest-tract entry: --ibd_longest then stops with a message
 #pragma weak nghmm_chain_ibd_longest
+// ... and without the long-tract posterior entry: --ibd_long then stops with a message
+#pragma weak nghmm_chain_ibd_long
 // ... and without the support entries: --ibd_support then stops with a message
 #pragma weak nghmm_tract_support
 #pragma weak nghmm_chain_tract_support
@@ -191,6 +199,16 @@ struct Params {  // ngsF-HMM.hpp:13-52
   bool ibd_longest = false, longest_sites = false;
   std::vector<double> longest;
   uint64_t longest_window = 0;
+  // --ibd_long L1,L2,...: PREFIX.ibd.long.regions and PREFIX.ibd.long.sites after the final decode
+  // (nghmm_chain_ibd_long): per threshold the posterior of every site of lying in an IBD tract of
+  // at least that length, summed per individual and chromosome, or with --long_window N per window
+  // of N sites that restarts at every chromosome start, and per site over the individuals with
+  // the count of those at or above --long_thresh; --long_post adds PREFIX.ibd.long.post, the
+  // posteriors themselves as raw doubles [K][I][S]; the thresholds are Mb, or sites with --long_sites
+  bool ibd_long = false, long_sites = false, long_post = false;
+  std::vector<double> long_len;
+  uint64_t long_window = 0;
+  double long_thresh = 0.5;
   // --ibd_support: PREFIX.ibd.support after the final decode -- per Viterbi tract the joint
   // posterior of IBD throughout, its log-odds against non-IBD throughout and the weakest site
   // (nghmm_chain_tract_support)
@@ -1783,6 +1801,81 @@ void write_ibd_longest(const Params& P, Cohort& C) {
   if (fclose(fh) != 0) fatal(__FUNCTION__, "cannot write the longest-tract output file!");
 }
 
+// PREFIX.ibd.long.regions: a header line, then per individual, region and threshold "ind chr
+// first_pos last_pos n_sites min_len exp_sites exp_mb" (tab-separated; IDs, regions and order as
+// --ibd_by_length writes them, with --long_window for the windows): the expected sites and Mb of
+// the region inside IBD tracts of at least min_len (Mb, or sites with --long_sites).
+// PREFIX.ibd.long.sites: a header line, then per site and threshold "chr pos min_len count
+// post_sum": the individuals whose posterior of lying in such a tract reaches --long_thresh, and
+// the sum of the posteriors.  With --long_post PREFIX.ibd.long.post: the posteriors as raw doubles
+// [K][I][S].  Doubles as %.10g; everything conditional on the final indF, alpha and frequencies.
+void write_ibd_long(const Params& P, Cohort& C) {
+  if (!nghmm_chain_ibd_long) fatal(__FUNCTION__, "--ibd_long: the library has no nghmm_chain_ibd_long!");
+  const uint64_t I = P.n_ind, S = P.n_sites, K = P.long_len.size();
+  std::vector<uint64_t> begin, end;
+  std::vector<size_t> chrom;   // the chromosome run of every region
+  for (size_t c = 0; c < P.chrom_first.size(); c++) {
+    const uint64_t a = P.chrom_first[c], b = c + 1 < P.chrom_first.size() ? P.chrom_first[c + 1] : S;
+    const uint64_t w = P.long_window ? P.long_window : b - a;
+    for (uint64_t lo = a; lo < b; lo += w) {
+      begin.push_back(lo);
+      end.push_back(b - lo < w ? b : lo + w);
+      chrom.push_back(c);
+    }
+  }
+  const uint64_t R = begin.size();
+  std::vector<nghmm_long_region_stat> st((size_t)I * R * K);
+  std::vector<nghmm_long_site_stat> ss((size_t)S * K);
+  std::vector<double> post(P.long_post ? (size_t)K * I * S : 0);
+  check(nghmm_chain_ibd_long(C.hs.data(), C.n(), P.long_sites ? 0 : NGHMM_LONG_MB, (uint32_t)K, P.long_len.data(),
+                             P.long_thresh, R, begin.data(), end.data(), st.data(), ss.data(),
+                             P.long_post ? post.data() : nullptr),
+        "ibd_long");
+  {
+    const std::string name = P.prefix + ".ibd.long.regions";
+    FILE* fh = fopen(name.c_str(), "w");
+    if (!fh) fatal(__FUNCTION__, "cannot open long-tract region output file!");
+    setvbuf(fh, nullptr, _IOFBF, 1 << 22);
+    fputs("ind\tchr\tfirst_pos\tlast_pos\tn_sites\tmin_len\texp_sites\texp_mb\n", fh);
+    for (uint64_t i = 0; i < I; i++) {
+      const std::string id = P.ind_names.empty() ? "ind" + std::to_string(i) : P.ind_names[i];
+      for (uint64_t r = 0; r < R; r++)
+        for (uint64_t k = 0; k < K; k++) {
+          const nghmm_long_region_stat& t = st[(i * R + r) * K + k];
+          fprintf(fh, "%s\t%s\t%llu\t%llu\t%llu\t%.10g\t%.10g\t%.10g\n", id.c_str(),
+                  P.chrom_name[chrom[r]].c_str(), (unsigned long long)P.site_pos[begin[r]],
+                  (unsigned long long)P.site_pos[end[r] - 1], (unsigned long long)(end[r] - begin[r]),
+                  P.long_len[k], t.sites, t.mb);
+        }
+    }
+    if (fclose(fh) != 0) fatal(__FUNCTION__, "cannot write the long-tract region output file!");
+  }
+  {
+    const std::string name = P.prefix + ".ibd.long.sites";
+    FILE* fh = fopen(name.c_str(), "w");
+    if (!fh) fatal(__FUNCTION__, "cannot open long-tract site output file!");
+    setvbuf(fh, nullptr, _IOFBF, 1 << 22);
+    fputs("chr\tpos\tmin_len\tcount\tpost_sum\n", fh);
+    for (size_t c = 0; c < P.chrom_first.size(); c++) {
+      const uint64_t a = P.chrom_first[c], b = c + 1 < P.chrom_first.size() ? P.chrom_first[c + 1] : S;
+      for (uint64_t s = a; s < b; s++)
+        for (uint64_t k = 0; k < K; k++) {
+          const nghmm_long_site_stat& t = ss[s * K + k];
+          fprintf(fh, "%s\t%llu\t%.10g\t%llu\t%.10g\n", P.chrom_name[c].c_str(),
+                  (unsigned long long)P.site_pos[s], P.long_len[k], (unsigned long long)t.count, t.sum);
+        }
+    }
+    if (fclose(fh) != 0) fatal(__FUNCTION__, "cannot write the long-tract site output file!");
+  }
+  if (P.long_post) {
+    const std::string name = P.prefix + ".ibd.long.post";
+    FILE* fh = fopen(name.c_str(), "wb");
+    if (!fh) fatal(__FUNCTION__, "cannot open long-tract posterior output file!");
+    if (fwrite(post.data(), sizeof(double), post.size(), fh) != post.size() || fclose(fh) != 0)
+      fatal(__FUNCTION__, "cannot write the long-tract posterior output file!");
+  }
+}
+
 // PREFIX.ibd.sharing: a header line, then per pair of individuals i <= j, in (i, j) order,
 // "IND_ID1 IND_ID2 vit_both post_both post_prod" (tab-separated; IDs as --ibd_bed names them): the
 // sites, genome-wide, at which both are IBD in the decoded path, at which both posteriors reach
@@ -2110,6 +2203,9 @@ void parse_cmd_args(Params& P, int argc, char** argv) {  // parse_args.cpp:41-22
       {"by_length_window", required_argument, nullptr, 1036},
       {"ibd_longest", required_argument, nullptr, 1037}, {"longest_sites", no_argument, nullptr, 1038},
       {"longest_window", required_argument, nullptr, 1039},
+      {"ibd_long", required_argument, nullptr, 1040}, {"long_sites", no_argument, nullptr, 1041},
+      {"long_window", required_argument, nullptr, 1042}, {"long_thresh", required_argument, nullptr, 1043},
+      {"long_post", no_argument, nullptr, 1044},
       {0, 0, 0, 0}};
   long taus_kat = 0;
   bool parse_kat = false, se_kat = false;
@@ -2217,6 +2313,34 @@ void parse_cmd_args(Params& P, int argc, char** argv) {  // parse_args.cpp:41-22
         if (atoll(optarg) < 1) fatal(__FUNCTION__, "invalid --longest_window (sites per window)!");
         P.longest_window = strtoull(optarg, nullptr, 10);
         break;
+      case 1040: {   // L1,L2,...: every field a number; the rest is checked once the unit is known
+        P.ibd_long = true;
+        P.long_len.clear();
+        const char* q = optarg;
+        while (true) {
+          char* e = nullptr;
+          const double v = strtod(q, &e);
+          if (e == q || (*e != ',' && *e != '\0'))
+            fatal(__FUNCTION__, "invalid --ibd_long (a comma-separated list of minimum lengths)!");
+          P.long_len.push_back(v);
+          if (*e == '\0') break;
+          q = e + 1;
+        }
+        break;
+      }
+      case 1041: P.long_sites = true; break;
+      case 1042:
+        if (atoll(optarg) < 1) fatal(__FUNCTION__, "invalid --long_window (sites per window)!");
+        P.long_window = strtoull(optarg, nullptr, 10);
+        break;
+      case 1043: {
+        char* e = nullptr;
+        P.long_thresh = strtod(optarg, &e);
+        if (e == optarg || *e != '\0' || !(P.long_thresh >= 0 && P.long_thresh <= 1))
+          fatal(__FUNCTION__, "invalid --long_thresh (a probability in [0, 1])!");
+        break;
+      }
+      case 1044: P.long_post = true; break;
       case 1026: {   // a,b,...: every field a number in [0, 1]
         P.freq_levels.clear();
         P.freq_levels_given = true;
@@ -2387,6 +2511,22 @@ void parse_cmd_args(Params& P, int argc, char** argv) {  // parse_args.cpp:41-22
   }
   if (!P.ibd_longest && (P.longest_window || P.longest_sites))
     warn(__FUNCTION__, "--longest_window and --longest_sites are only used by --ibd_longest");
+  if (P.ibd_long) {
+    if (!nghmm_chain_ibd_long) fatal(__FUNCTION__, "--ibd_long: the library has no nghmm_chain_ibd_long!");
+    if (P.long_len.empty() || P.long_len.size() > 8)
+      fatal(__FUNCTION__, "invalid --ibd_long (1 to 8 minimum lengths)!");
+    for (size_t k = 0; k < P.long_len.size(); k++) {
+      const double v = P.long_len[k];
+      const bool ok = std::isfinite(v) && (P.long_sites ? (v >= 1 && v == std::floor(v)) : v >= 0) &&
+                      (k == 0 || v > P.long_len[k - 1]);
+      if (!ok)
+        fatal(__FUNCTION__, P.long_sites
+                                ? "invalid --ibd_long (strictly increasing whole numbers of sites >= 1)!"
+                                : "invalid --ibd_long (strictly increasing lengths in Mb >= 0)!");
+    }
+  }
+  if (!P.ibd_long && (P.long_window || P.long_sites || P.long_post))
+    warn(__FUNCTION__, "--long_window, --long_sites, --long_thresh and --long_post are only used by --ibd_long");
   if (P.min_iters < 1 || P.max_iters < 1 || P.min_iters >= P.max_iters)
     fatal(__FUNCTION__, "invalid number of iterations!");
   if (P.n_threads < 1) fatal(__FUNCTION__, "invalid number of threads!");
@@ -2420,8 +2560,8 @@ void parse_cmd_args(Params& P, int argc, char** argv) {  // parse_args.cpp:41-22
       fatal(__FUNCTION__, "number of lines in --ind_names file is not --n_ind!");
     if (!P.ibd_bed && !P.sample_paths && !P.indF_se && !P.ibd_summary && !P.ibd_sharing && !P.ibd_support &&
         !P.ibd_bounds && !P.geno_summary && !P.ibd_expect && !P.ibd_moments && !P.ibd_by_length &&
-        !P.ibd_longest)
-      warn(__FUNCTION__, "--ind_names is only used by --ibd_bed, --sample_paths, --indF_se, --ibd_summary, --ibd_sharing, --ibd_support, --ibd_bounds, --geno_summary, --ibd_expect, --ibd_moments, --ibd_by_length and --ibd_longest");
+        !P.ibd_longest && !P.ibd_long)
+      warn(__FUNCTION__, "--ind_names is only used by --ibd_bed, --sample_paths, --indF_se, --ibd_summary, --ibd_sharing, --ibd_support, --ibd_bounds, --geno_summary, --ibd_expect, --ibd_moments, --ibd_by_length, --ibd_longest and --ibd_long");
   }
   P.prefix = P.out_prefix;
 }
@@ -2526,6 +2666,7 @@ void finish_run(Params& P, Cohort& C) {
   if (P.ibd_moments) write_ibd_moments(P, C);
   if (P.ibd_by_length) write_ibd_by_length(P, C);
   if (P.ibd_longest) write_ibd_longest(P, C);
+  if (P.ibd_long) write_ibd_long(P, C);
   if (P.verbose >= 2)  // (not a line of the reference's)
     fprintf(P.out, "> decoded in %.2f s, output files written in %.2f s\n", t1 - t0, omp_get_wtime() - t1);
 }
@@ -2650,6 +2791,7 @@ int main(int argc, char** argv) {
         runs[r].ibd_moments = P.ibd_moments && r == best;
         runs[r].ibd_by_length = P.ibd_by_length && r == best;
         runs[r].ibd_longest = P.ibd_longest && r == best;
+        runs[r].ibd_long = P.ibd_long && r == best;
         finish_run(runs[r], cs[r]);
       }
       fclose(runs[r].out);
@@ -2682,6 +2824,11 @@ int main(int argc, char** argv) {
       if (P.ibd_moments) exts.push_back(".ibd.moments");
       if (P.ibd_by_length) exts.push_back(".ibd.bylength");
       if (P.ibd_longest) exts.push_back(".ibd.longest");
+      if (P.ibd_long) {
+        exts.push_back(".ibd.long.regions");
+        exts.push_back(".ibd.long.sites");
+        if (P.long_post) exts.push_back(".ibd.long.post");
+      }
       for (unsigned k = 1; P.sample_paths && k <= P.sample_keep; k++) {
         char tag[32];
         snprintf(tag, sizeof tag, ".sample_%02u.ibd", k);

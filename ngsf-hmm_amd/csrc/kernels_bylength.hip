@@ -47,9 +47,13 @@ struct WalkArgs {
   double* __restrict__ map;
   double* __restrict__ qtail;
   uint32_t* __restrict__ nblk;
+  double* __restrict__ pi;   // (PI only) the posterior of the IBD state, a plane like sigma
 };
 
-// The forward recomputation, the beta step and the four products are k_expect_walk's.
+// The forward recomputation, the beta step and the four products are k_expect_walk's.  PI: the
+// posterior x01 + x11, which the walk forms anyway, goes to a plane of its own (kernels_long.hip);
+// without it the kernel is what it was.
+template <bool PI>
 __global__ void __launch_bounds__(64, 2)
 k_bylength_walk(const WalkArgs A) {
   const uint64_t i = blockIdx.x / A.C;
@@ -140,6 +144,7 @@ k_bylength_walk(const WalkArgs A) {
         A.sigma[o] = real ? sg : 0.0;
         A.q[o] = (real && !blocked) ? L11 : kBlocked;
         A.m[o] = (real && !blocked) ? rho : 0.0;
+        if (PI) A.pi[o] = real ? x01 + x11 : 0.0;
       }
       if (real) {   // (a padding site is the identity)
         if (blocked) {
@@ -462,13 +467,15 @@ k_bylength_finish(const ExpectRegion* __restrict__ reg, uint64_t n_reg, uint64_t
 
 // exact mode: the forward array as k_expect_exact fills it; the backward recursion right to left
 // with sigma_s, ln rho_s and rem_s per site; Q_s and n_s left to right; then every region's terms
-// added to 0 from its last site to its first.
+// added to 0 from its last site to its first.  PI: x01 + x11 per site goes to the plane pi [S][I].
+template <bool PI>
 __global__ void __launch_bounds__(64)
 k_bylength_exact(const double* __restrict__ eprob, const double* __restrict__ pos, double* __restrict__ fw,
                  uint64_t S, uint64_t I, const double* __restrict__ indF, const double* __restrict__ alpha,
                  int mb, uint32_t K, const ByLenCells cl, const uint32_t* __restrict__ btab,
                  const double* __restrict__ cum, const ExpectRegion* __restrict__ reg, uint64_t n_reg,
-                 ByLenRec* __restrict__ out, double* __restrict__ qmax, int* __restrict__ flags) {
+                 ByLenRec* __restrict__ out, double* __restrict__ qmax, int* __restrict__ flags,
+                 double* __restrict__ pi) {
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= I) return;
   const double f = indF[i], al = alpha[i];
@@ -516,6 +523,7 @@ k_bylength_exact(const double* __restrict__ eprob, const double* __restrict__ po
     const double rho = (start || !(L11 > NGH_NEG_INF)) ? 0.0 : det_exp(L11);
     const bool blocked = !(rho > 0.0);
     cl.sigma[s * I + i] = start ? x01 + x11 : x01;
+    if (PI) pi[s * I + i] = x01 + x11;
     cl.q[s * I + i] = blocked ? kBlocked : L11;
     cl.m[s * I + i] = x;
     x = blocked ? 0.0 : rho * ((mb ? d : 1.0) + x);
@@ -577,7 +585,7 @@ uint64_t bylength_cell_count(const FastState* fs, uint64_t S, uint64_t I) {
 
 bool bylength_fast_cells(FastState& fs, hipStream_t st, const double* d_indF, const double* d_alpha,
                          bool has_vin, bool mb, const ByLenCells& cells, const ByLenChunks& ch,
-                         const double* carry_in, double* carry_out, double* qmax) {
+                         const double* carry_in, double* carry_out, double* qmax, double* pi) {
   if (fs.T == 0 || fs.T % CK != 0) return false;
   WalkArgs A;
   A.e_il = fs.e_il;
@@ -597,8 +605,10 @@ bool bylength_fast_cells(FastState& fs, hipStream_t st, const double* d_indF, co
   A.map = ch.map;
   A.qtail = ch.qtail;
   A.nblk = ch.nblk;
+  A.pi = pi;
   const dim3 grid((unsigned)(fs.I * fs.C)), block(64);
-  hipLaunchKernelGGL(k_bylength_walk, grid, block, 0, st, A);
+  if (pi) hipLaunchKernelGGL(k_bylength_walk<true>, grid, block, 0, st, A);
+  else hipLaunchKernelGGL(k_bylength_walk<false>, grid, block, 0, st, A);
   hipLaunchKernelGGL(k_bylength_scan, dim3((unsigned)fs.I), block, 0, st, fs.C, ch.map, ch.qtail, ch.nblk,
                      carry_in, carry_out, ch.endM, ch.endD, ch.q0, ch.n0);
   hipLaunchKernelGGL(k_bylength_fill, grid, block, 0, st, fs.T, fs.S, fs.I, fs.C, mb ? 1 : 0, fs.pos_il,
@@ -649,9 +659,14 @@ void launch_bylength_exact(hipStream_t st, const double* eprob, const double* po
                            uint64_t I, const double* d_indF, const double* d_alpha, bool mb, uint32_t K,
                            const ByLenCells& cells, const uint32_t* btab, const double* cum,
                            const ExpectRegion* d_reg, uint64_t n_reg, ByLenRec* d_out, double* qmax,
-                           int* d_flags) {
-  hipLaunchKernelGGL(k_bylength_exact, dim3((unsigned)((I + 63) / 64)), dim3(64), 0, st, eprob, pos, fw, S, I,
-                     d_indF, d_alpha, mb ? 1 : 0, K, cells, btab, cum, d_reg, n_reg, d_out, qmax, d_flags);
+                           int* d_flags, double* pi) {
+  const dim3 grid((unsigned)((I + 63) / 64)), block(64);
+  if (pi)
+    hipLaunchKernelGGL(k_bylength_exact<true>, grid, block, 0, st, eprob, pos, fw, S, I, d_indF, d_alpha,
+                       mb ? 1 : 0, K, cells, btab, cum, d_reg, n_reg, d_out, qmax, d_flags, pi);
+  else
+    hipLaunchKernelGGL(k_bylength_exact<false>, grid, block, 0, st, eprob, pos, fw, S, I, d_indF, d_alpha,
+                       mb ? 1 : 0, K, cells, btab, cum, d_reg, n_reg, d_out, qmax, d_flags, pi);
 }
 
 }  // namespace nghmm

@@ -69,9 +69,11 @@ struct ByLenHalo {
 //   carry_in   [I][2]: M, D at the handle's last site (null: 0, nothing follows)
 //   carry_out  [I][2]: M, D at the site in front of the handle's first (null: not wanted)
 //   qmax       [I C]: the largest |Q| of every wave
+//   pi         a plane like sigma for the posterior of the IBD state (null: not wanted; it may be
+//              cells.d when mb is false, which then stays untouched)
 bool bylength_fast_cells(FastState& fs, hipStream_t st, const double* d_indF, const double* d_alpha,
                          bool has_vin, bool mb, const ByLenCells& cells, const ByLenChunks& ch,
-                         const double* carry_in, double* carry_out, double* qmax);
+                         const double* carry_in, double* carry_out, double* qmax, double* pi = nullptr);
 // Q, n, rem of the handle's first H sites, [I][H] each
 void bylength_fast_halo(FastState& fs, hipStream_t st, bool mb, const ByLenCells& cells, uint64_t H,
                         double* q, uint32_t* n, double* rem);
@@ -85,11 +87,12 @@ bool bylength_fast_terms(FastState& fs, hipStream_t st, bool mb, uint32_t K, con
                          uint64_t n_pieces, ByLenRec* d_piece, ByLenRec* d_out);
 
 // exact mode: one lane per individual in log space, serial over the sites.  btab [K][S] and cum [S]
-// site-major; cells [S][I]; fw [S + 1][I][2] as launch_expect_exact; qmax [I].
+// site-major; cells [S][I]; fw [S + 1][I][2] as launch_expect_exact; qmax [I]; pi [S][I] the
+// posterior of the IBD state (null: not wanted).  n_reg = 0 fills the cells alone.
 void launch_bylength_exact(hipStream_t st, const double* eprob, const double* pos, double* fw, uint64_t S,
                            uint64_t I, const double* d_indF, const double* d_alpha, bool mb, uint32_t K,
                            const ByLenCells& cells, const uint32_t* btab, const double* cum,
                            const ExpectRegion* d_reg, uint64_t n_reg, ByLenRec* d_out, double* qmax,
-                           int* d_flags);
+                           int* d_flags, double* pi = nullptr);
 
 }  // namespace nghmm

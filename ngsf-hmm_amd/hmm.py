@@ -177,6 +177,9 @@ def load_library():
         "nghmm_ibd_longest": (i32, [vp, i32, u32, dp, u64, C.POINTER(u64), C.POINTER(u64), vp]),
         "nghmm_chain_ibd_longest": (i32, [C.POINTER(vp), i32, i32, u32, dp, u64, C.POINTER(u64),
                                           C.POINTER(u64), vp]),
+        "nghmm_ibd_long": (i32, [vp, i32, u32, dp, d, u64, C.POINTER(u64), C.POINTER(u64), vp, vp, dp]),
+        "nghmm_chain_ibd_long": (i32, [C.POINTER(vp), i32, i32, u32, dp, d, u64, C.POINTER(u64),
+                                       C.POINTER(u64), vp, vp, dp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -225,7 +228,9 @@ EXPORTED_SYMBOLS = [
     "nghmm_ibd_moments", "nghmm_chain_ibd_moments",
     "nghmm_ibd_by_length", "nghmm_chain_ibd_by_length", "nghmm_debug_bylength_qmax",
     "nghmm_ibd_longest", "nghmm_chain_ibd_longest",
+    "nghmm_ibd_long",
 ]
+# (nghmm_chain_ibd_long is declared in include/nghmm_chain_long.h)
 
 OBJECTIVE_FN = C.CFUNCTYPE(C.c_double, C.c_uint32, C.c_double, C.c_double, C.c_void_p)
 
@@ -752,6 +757,20 @@ def _ibd_by_length(call, check, n_ind, n_sites, min_len, unit, regions, dtype=No
     """What ibd_by_length and ibd_longest share: the checks of unit, thresholds and regions, the
     record array [I][R][K] of `dtype` and the call; mb_flag is the entry's own bit for Mb."""
     u64p = C.POINTER(C.c_uint64)
+    L, reg = _by_length_args(n_sites, min_len, unit, regions, name)
+    R, K = len(reg), len(L)
+    begin, end = np.ascontiguousarray(reg[:, 0]), np.ascontiguousarray(reg[:, 1])
+    stats = np.zeros((n_ind, R, K), dtype=BYLENGTH_DTYPE if dtype is None else dtype)
+    mb_flag = BYLENGTH_MB if mb_flag is None else mb_flag
+    check(call(mb_flag if unit == "mb" else 0, K, _dp(L) if K else None, R,
+               begin.ctypes.data_as(u64p) if R else None, end.ctypes.data_as(u64p) if R else None,
+               C.c_void_p(stats.ctypes.data) if R and K else None))
+    return stats
+
+
+def _by_length_args(n_sites, min_len, unit, regions, name):
+    """The argument checks of ibd_by_length, ibd_longest and ibd_long: (thresholds float64 [K],
+    regions uint64 [R][2]); regions None is one region over all sites."""
     if unit not in ("sites", "mb"):
         raise NgsFHMMError(-10, f"{name}: unit is 'sites' or 'mb'")
     L = np.ascontiguousarray(np.atleast_1d(np.asarray(min_len, dtype=np.float64)))
@@ -768,14 +787,7 @@ def _ibd_by_length(call, check, n_ind, n_sites, min_len, unit, regions, dtype=No
             raise NgsFHMMError(-10, f"{name}: regions is an [R][2] array of site indices "
                                     "(begin, end)")
         reg = reg.astype(np.uint64)
-    R, K = len(reg), len(L)
-    begin, end = np.ascontiguousarray(reg[:, 0]), np.ascontiguousarray(reg[:, 1])
-    stats = np.zeros((n_ind, R, K), dtype=BYLENGTH_DTYPE if dtype is None else dtype)
-    mb_flag = BYLENGTH_MB if mb_flag is None else mb_flag
-    check(call(mb_flag if unit == "mb" else 0, K, _dp(L) if K else None, R,
-               begin.ctypes.data_as(u64p) if R else None, end.ctypes.data_as(u64p) if R else None,
-               C.c_void_p(stats.ctypes.data) if R and K else None))
-    return stats
+    return L, reg
 
 
 def by_length_classes(stats):
@@ -801,6 +813,77 @@ class LongestStat(C.Structure):      # nghmm_longest_stat (include/nghmm.h)
 
 LONGEST_DTYPE = np.dtype([(n, np.float64) for n, _ in LongestStat._fields_])
 assert LONGEST_DTYPE.itemsize == C.sizeof(LongestStat) == 16
+
+
+LONG_MB = 1            # nghmm_ibd_long: thresholds in Mb instead of sites
+
+
+class LongRegionStat(C.Structure):   # nghmm_long_region_stat (include/nghmm.h)
+    _fields_ = [(n, C.c_double) for n in ("sites", "mb")]
+
+
+class LongSiteStat(C.Structure):     # nghmm_long_site_stat (include/nghmm.h)
+    _fields_ = [("sum", C.c_double), ("count", C.c_uint64)]
+
+
+LONG_REGION_DTYPE = np.dtype([(n, np.float64) for n, _ in LongRegionStat._fields_])
+LONG_SITE_DTYPE = np.dtype([("sum", np.float64), ("count", np.uint64)])
+assert LONG_REGION_DTYPE.itemsize == C.sizeof(LongRegionStat) == 16
+assert LONG_SITE_DTYPE.itemsize == C.sizeof(LongSiteStat) == 16
+
+
+def _ibd_long(call, check, n_ind, n_sites, min_len, unit, regions, sites, post, threshold):
+    """ibd_long of a handle or a chain: _ibd_by_length's argument checks, the arrays asked for,
+    the call."""
+    u64p = C.POINTER(C.c_uint64)
+    name = "ibd_long"
+    L, reg = _by_length_args(n_sites, min_len, unit, None if regions is False else regions, name)
+    if regions is False:
+        reg = reg[:0]
+    R, K = len(reg), len(L)
+    out = {}
+    if R:
+        out["regions"] = np.zeros((n_ind, R, K), dtype=LONG_REGION_DTYPE)
+    if sites:
+        out["sites"] = np.zeros((n_sites, K), dtype=LONG_SITE_DTYPE)
+    if post:
+        out["post"] = np.zeros((K, n_ind, n_sites))
+    begin, end = np.ascontiguousarray(reg[:, 0]), np.ascontiguousarray(reg[:, 1])
+    ptr = lambda key: C.c_void_p(out[key].ctypes.data) if key in out and K else None
+    check(call(LONG_MB if unit == "mb" else 0, K, _dp(L) if K else None, float(threshold), R,
+               begin.ctypes.data_as(u64p) if R else None, end.ctypes.data_as(u64p) if R else None,
+               ptr("regions"), ptr("sites"), _dp(out["post"]) if post and K else None))
+    return out
+
+
+def long_tracts(post_k, pos_dist, threshold=0.5, min_sites=1):
+    """Tracts called from one plane of ibd_long's post, P_k [I][S]: the maximal runs of
+    P_k >= threshold, cut at chromosome starts, of at least min_sites sites, in TRACT_DTYPE as
+    ibd_tracts returns them (ordered by (ind, first_site); post_sum = the run's sum of P_k), so
+    that bed_lines and tract_support take them as they are."""
+    p = np.asarray(post_k, dtype=np.float64)
+    if p.ndim != 2 or p.shape[1] != len(pos_dist):
+        raise NgsFHMMError(-10, "long_tracts: post_k is [I][S] and pos_dist [S]")
+    I, S = p.shape
+    on = p >= threshold
+    cs = np.isinf(np.asarray(pos_dist, dtype=np.float64))
+    if S:
+        cs[0] = True
+    prev = np.concatenate([np.zeros((I, 1), dtype=bool), on[:, :-1]], axis=1)
+    nxt_cs = np.r_[cs[1:], True] if S else cs
+    nxt = np.concatenate([on[:, 1:], np.zeros((I, 1), dtype=bool)], axis=1)
+    first = on & (~prev | cs[None, :])
+    last = on & (~nxt | nxt_cs[None, :])
+    ind, a = np.nonzero(first)
+    _, b = np.nonzero(last)
+    csum = np.concatenate([np.zeros((I, 1)), np.cumsum(np.where(on, p, 0.0), axis=1)], axis=1)
+    n = (b - a + 1).astype(np.uint64)
+    keep = n >= min_sites
+    out = np.empty(int(keep.sum()), dtype=TRACT_DTYPE)
+    out["ind"], out["first_site"], out["n_sites"] = ind[keep], a[keep], n[keep]
+    out["post_sum"] = (csum[ind, b + 1] - csum[ind, a])[keep]
+    out["post_mean"] = out["post_sum"] / np.maximum(out["n_sites"], 1)
+    return out
 
 
 def longest_classes(stats):
@@ -1387,6 +1470,17 @@ class NgsFHMM:
                               self.n_ind, self.n_sites, min_len, unit, regions, LONGEST_DTYPE,
                               "ibd_longest", LONGEST_MB)
 
+    def ibd_long(self, min_len, unit="sites", regions=None, sites=True, post=False, threshold=0.5):
+        """The posterior of every site of lying in an IBD tract of at least min_len[k], exactly
+        (nghmm_ibd_long).  min_len and unit as ibd_by_length takes them.  Returns a dict of the
+        arrays asked for: "regions" [I][R][K] of LONG_REGION_DTYPE -- sites and mb, the expected
+        sites and Mb of the region inside such tracts (regions as ibd_summary takes them, None =
+        one region over all sites, False = none); "sites" [S][K] of LONG_SITE_DTYPE -- sum over
+        the individuals and the count of those at or above threshold (sites=True); "post"
+        [K][I][S], each plane like marg_prob (post=True).  long_tracts calls tracts from a plane."""
+        return _ibd_long(lambda *a: self.lib.nghmm_ibd_long(self._h, *a), self._check, self.n_ind,
+                         self.n_sites, min_len, unit, regions, sites, post, threshold)
+
     def by_length_qmax(self):
         """The largest |Q| the last ibd_by_length met (nghmm_debug_bylength_qmax): times 2^-53 the
         absolute error in the exponent of a window's probability."""
@@ -1596,6 +1690,15 @@ class Chain:
         return _ibd_by_length(
             lambda *a: self.lib.nghmm_chain_ibd_by_length(self._arr, len(self.handles), *a),
             self.handles[0]._check, self.n_ind, self.n_sites, min_len, unit, regions)
+
+    def ibd_long(self, min_len, unit="sites", regions=None, sites=True, post=False, threshold=0.5):
+        """NgsFHMM.ibd_long over the chain (nghmm_chain_ibd_long): global site indices, a region
+        across a shard boundary is one region, a window may reach into the neighbouring shard on
+        either side but not past it; within rounding of a single handle's values."""
+        self._members_open()
+        return _ibd_long(lambda *a: self.lib.nghmm_chain_ibd_long(self._arr, len(self.handles), *a),
+                         self.handles[0]._check, self.n_ind, self.n_sites, min_len, unit, regions,
+                         sites, post, threshold)
 
     def ibd_longest(self, min_len, unit="sites", regions=None):
         """NgsFHMM.ibd_longest over the chain (nghmm_chain_ibd_longest): global site indices; the
