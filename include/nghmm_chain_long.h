@@ -1,9 +1,11 @@
 /*
  * nghmm_chain_long.h -- nghmm_ibd_long (include/nghmm.h) over a chain of site shards.
  *
- * A header of its own: tests/replica_util.py's battery covers every output entry point of
- * include/nghmm.h that has a chain twin there, and this call's replica test is
- * tests/test_gpu_long.py's own.
+ * A header of its own for the size of include/nghmm.h alone: it is a public header like that one.
+ * tests/test_replica_battery_cpu.py and tests/test_chain_battery_cpu.py read every header under
+ * include/ but nghmm_debug.h, so nghmm_ibd_long and this twin are held to the replica, layout and
+ * chain batteries (tests/replica_util.py, tests/layout_util.py, tests/chain_util.py) like every
+ * other output entry point.
  */
 #ifndef NGHMM_CHAIN_LONG_H
 #define NGHMM_CHAIN_LONG_H

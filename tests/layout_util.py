@@ -18,7 +18,8 @@ the same data at another layout, key by key, by the rules of RULES:
              of the yardstick: the triangle inequality), times ctx.scale for longer data.
 
 No bound here is taken from a device's output.  tests/test_layouts_cpu.py keeps RULES total over
-the battery's keys."""
+the battery's keys.  tests/chain_util.py reuses the rules, with named overrides, for a chain of
+site shards against one handle."""
 import collections
 import contextlib
 import math
@@ -30,6 +31,7 @@ import bounds_util
 import bylength_util
 import expect_util as xu
 import info_util
+import long_util
 import moments_util
 import replica_util as ru
 import sharing_util
@@ -512,6 +514,36 @@ def _by_unit(table):
     return rule
 
 
+def _array(rep, key, got, ref, tol, scale=1):
+    """A plain array within scale x 2 x tol of the reference handle's."""
+    rep.need(f"{key} shape", got.shape == ref.shape and got.dtype == ref.dtype)
+    rep.need(f"{key} finite", bool(np.isfinite(got).all()))
+    if got.shape == ref.shape:
+        rep.add(key, _ratio(np.abs(got - ref), 2 * scale * tol))
+
+
+def rule_long(rep, name, got, ref, ctx):
+    """tests/test_gpu_long.py: the region records by long_util.TOL per unit and field; post and the
+    site records' sum by its "post" and "sum" (twice over, times ctx.scale, as every tolerance
+    rule); count restated as (post >= 0.5).sum of the handle's OWN post, which the battery asks for
+    wherever it asks for the site records."""
+    for k in _keys(got, name):
+        unit, part = k.split(".")[1], k.split(".")[-1]
+        tol = long_util.TOL[unit]
+        if part == "regions":
+            _fields(rep, k, got[k], ref[k], tol, ctx.scale)
+        elif part == "post":
+            _array(rep, k, got[k], ref[k], tol["post"], ctx.scale)
+        else:
+            rep.need(f"{k} part", part == "sites", "an output that ibd_long does not have")
+            _array(rep, f"{k} sum", got[k]["sum"], ref[k]["sum"], tol["sum"], ctx.scale)
+            own = k[:-len("sites")] + "post"
+            rep.need(f"{k} post", own in got, "site records without the handle's own post")
+            if own in got:
+                rep.need(f"{k} count", np.array_equal(got[k]["count"], (got[own] >= 0.5).sum(axis=1).T),
+                         "not (post >= 0.5).sum of the handle's own post")
+
+
 # battery key (its first component) -> rule
 RULES = collections.OrderedDict([
     ("indF", rule_bytes), ("alpha", rule_bytes), ("freq", rule_bytes), ("gl", rule_bytes),
@@ -524,7 +556,7 @@ RULES = collections.OrderedDict([
     ("mstep_freq", rule_mstep_freq),
     ("tract_support", rule_support), ("tract_bounds", rule_bounds), ("obs_info", rule_info),
     ("ibd_expect", rule_expect), ("ibd_moments", _by_unit(moments_util.COHORT_TOL)),
-    ("ibd_by_length", _by_unit(bylength_util.TOL)),
+    ("ibd_by_length", _by_unit(bylength_util.TOL)), ("ibd_long", rule_long),
 ])
 
 # every tolerance the rules import or state, for tests/test_layouts_cpu.py
@@ -535,21 +567,25 @@ TOLERANCES = {
     **{f"SITE_TOL.{k}": v for k, v in xu.SITE_TOL.items()},
     **{f"COHORT_TOL.{u}.{k}": v for u, d in moments_util.COHORT_TOL.items() for k, v in d.items()},
     **{f"bylength.TOL.{u}.{k}": v for u, d in bylength_util.TOL.items() for k, v in d.items()},
+    **{f"long.TOL.{u}.{k}": v for u, d in long_util.TOL.items() for k, v in d.items()},
 }
 
 
-def rule_of(key):
-    """The names of the rules that own a battery key: exactly one, or RULES is wrong."""
-    return [name for name in RULES if key == name or key.startswith(name + ".")]
+def rule_of(key, rules=None):
+    """The names of the rules that own a battery key: exactly one, or RULES is wrong.
+    rules: another table in RULES' place (tests/chain_util.CHAIN_RULES)."""
+    return [name for name in (RULES if rules is None else rules) if key == name or key.startswith(name + ".")]
 
 
-def compare(got, ref, ctx):
-    """Both batteries (array form) by RULES.  Returns the Report; the caller prints and asserts."""
+def compare(got, ref, ctx, rules=None):
+    """Both batteries (array form) by RULES, or by the table given.  Returns the Report; the caller
+    prints and asserts."""
+    rules = RULES if rules is None else rules
     rep = Report()
     rep.need("keys", list(got) == list(ref), "the two batteries have other keys")
     for k in got:
-        rep.need(f"{k} rule", len(rule_of(k)) == 1, "no rule, or two")
-    for name, rule in RULES.items():
+        rep.need(f"{k} rule", len(rule_of(k, rules)) == 1, "no rule, or two")
+    for name, rule in rules.items():
         if _keys(got, name):
             rule(rep, name, got, ref, ctx)
     return rep

@@ -6,9 +6,13 @@ handle loaded with the same data, so two batteries are compared with ==, key by 
 tolerance (both modes are deterministic; post_prod's split plan is a function of
 (I, site_begin, site_end) alone).  The layout tests (tests/test_gpu_layouts.py) ask for the same
 battery as arrays and compare two handles of different lane layouts by tests/layout_util.RULES.
+The chain tests (tests/test_gpu_chain_outputs.py) run it on a pkg.Chain of site shards -- every
+call that has an nghmm_chain_* twin, under the same keys -- and compare with one handle by
+tests/chain_util.CHAIN_RULES.
 
 COVERED is the set of C entry points the battery reaches; tests/test_replica_battery_cpu.py holds it
-against include/nghmm.h, so that an entry point added without a replica test fails there."""
+against the public headers under include/, so that an entry point added without a replica test
+fails there."""
 import collections
 import threading
 
@@ -25,7 +29,7 @@ COVERED = frozenset({
     "nghmm_ibd_tracts", "nghmm_sample_paths", "nghmm_tract_support", "nghmm_tract_bounds",
     "nghmm_freq_info", "nghmm_geno_smooth", "nghmm_obs_info", "nghmm_ibd_summary",
     "nghmm_ibd_expect", "nghmm_ibd_moments", "nghmm_ibd_by_length", "nghmm_ibd_longest",
-    "nghmm_ibd_sharing",
+    "nghmm_ibd_long", "nghmm_ibd_sharing",
 })
 
 # the region sets of the battery (expect_util.region_sets): chromosome starts, gaps, a region across
@@ -125,34 +129,56 @@ def info_points(n_ind):
     return np.linspace(0.1, 0.8, n_ind), np.geomspace(0.01, 2.0, n_ind)
 
 
-def battery(pkg, h, regions, arrays=False, estep_only=False, ranges=None):
+def members_agree(ch, which):
+    """indF or alpha of a chain: member 0's, after checking that every member holds its bytes."""
+    first = getattr(ch.handles[0], which)
+    for r, m in enumerate(ch.handles[1:], 1):
+        assert getattr(m, which).tobytes() == first.tobytes(), f"{which} of member {r} is not member 0's"
+    return first
+
+
+def battery(pkg, h, regions, arrays=False, estep_only=False, ranges=None, em_step=None, lengths=None):
     """On a handle that has parameters and emissions: iter_EM once, viterbi, then every output.
     regions: {name: [R][2]}; the per-cell outputs of geno_smooth and the site records are asked for
     with the first set only.  Returns an ordered dict of name -> bytes.
     arrays: name -> array instead (tests/layout_util.py compares within tolerances).
     estep_only: estep() in place of iter_EM() and no frequency step at the end, so that the
     parameters stay what the caller set (the L-BFGS-B M-step amplifies last-bit differences).
-    ranges: hand-made records [n][3] for tract_support / tract_bounds besides the decode's tracts."""
+    ranges: hand-made records [n][3] for tract_support / tract_bounds besides the decode's tracts.
+    em_step: {"freq", "ind_lkl"} of an EM step that the caller ran already (tests/chain_util.py's
+    prepare, which sets the parameters again after it): no E-step here, these two keys are taken
+    from it, and the frequency step at the end writes its frequencies alone.
+    lengths: {"ibd_by_length" / "ibd_long": {unit: thresholds}} in place of bylength_util.COHORT_LEN
+    (a chain refuses a threshold that reaches past a neighbouring shard).
+    h may be a pkg.Chain (with em_step): every call that has a chain twin, under the same keys;
+    Chain has no lkl, geno_posteriors, format_posteriors, gl or e_prob, and indF and alpha are
+    member 0's (every member must hold the same bytes)."""
     out = _Arrays() if arrays else collections.OrderedDict()
     I, S = h.n_ind, h.n_sites
-    if estep_only:
+    chain = isinstance(h, pkg.Chain)
+    assert em_step is not None or not chain, "a chain has no estep(): run chain_util.prepare first"
+    lengths = {"ibd_by_length": bu.COHORT_LEN, "ibd_long": bu.COHORT_LEN} if lengths is None else lengths
+    if em_step is not None:
+        pass
+    elif estep_only:
         h.estep()
     else:
         h.iter_EM()
     path = h.viterbi()
-    _records(out, "indF", h.indF)
-    _records(out, "alpha", h.alpha)
-    _records(out, "freq", h.freq)
-    _records(out, "ind_lkl", h.ind_lkl)
+    _records(out, "indF", members_agree(h, "indF") if chain else h.indF)
+    _records(out, "alpha", members_agree(h, "alpha") if chain else h.alpha)
+    _records(out, "freq", h.freq if em_step is None else em_step["freq"])
+    _records(out, "ind_lkl", h.ind_lkl if em_step is None else em_step["ind_lkl"])
     _records(out, "marg_prob", h.marg_prob)
     _records(out, "path", path)
-    _records(out, "e_prob", h.e_prob)
-    _records(out, "gl", h.gl)
-    _records(out, "geno_posteriors", h.geno_posteriors())
-    _records(out, "geno_posteriors.chunk", h.geno_posteriors(S // 5 + 1, S // 7))
-    _records(out, "format_posteriors", h.format_posteriors())
-    _records(out, "format_posteriors.part", h.format_posteriors(*posterior_part(I)))
-    _records(out, "lkl", h.lkl(*lkl_points(I)))
+    if not chain:
+        _records(out, "e_prob", h.e_prob)
+        _records(out, "gl", h.gl)
+        _records(out, "geno_posteriors", h.geno_posteriors())
+        _records(out, "geno_posteriors.chunk", h.geno_posteriors(S // 5 + 1, S // 7))
+        _records(out, "format_posteriors", h.format_posteriors())
+        _records(out, "format_posteriors.part", h.format_posteriors(*posterior_part(I)))
+        _records(out, "lkl", h.lkl(*lkl_points(I)))
 
     tv = h.ibd_tracts("viterbi")
     _records(out, "ibd_tracts.viterbi", tv)
@@ -174,8 +200,10 @@ def battery(pkg, h, regions, arrays=False, estep_only=False, ranges=None):
         _records(out, f"ibd_expect.{tag}", h.ibd_expect(reg, sites=first, viterbi=True))
         for u, L in bu.COHORT_LEN.items():
             _records(out, f"ibd_moments.{u}.{tag}", h.ibd_moments(reg, length=u))
-            _records(out, f"ibd_by_length.{u}.{tag}", h.ibd_by_length(L, unit=u, regions=reg))
+            _records(out, f"ibd_by_length.{u}.{tag}", h.ibd_by_length(lengths["ibd_by_length"][u], unit=u, regions=reg))
             _records(out, f"ibd_longest.{u}.{tag}", h.ibd_longest(L, unit=u, regions=reg))
+            _records(out, f"ibd_long.{u}.{tag}",
+                     h.ibd_long(lengths["ibd_long"][u], unit=u, regions=reg, sites=first, post=first))
         first = False
     _records(out, "ibd_sharing", h.ibd_sharing(("viterbi", "posterior")))
     _records(out, "ibd_sharing.range", h.ibd_sharing(("viterbi", "posterior"), 0.7, *sharing_range(S)))
@@ -184,7 +212,8 @@ def battery(pkg, h, regions, arrays=False, estep_only=False, ranges=None):
     # the frequency step on its own (it has a chain twin): from the posteriors of the iteration above
     h.mstep_freq(1)
     _records(out, "mstep_freq.freq", h.freq)
-    _records(out, "mstep_freq.e_prob", h.e_prob)
+    if em_step is None:
+        _records(out, "mstep_freq.e_prob", h.e_prob)
     return out
 
 

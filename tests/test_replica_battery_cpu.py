@@ -2,7 +2,7 @@
 checks its starts where no device is needed.
 
 Every output entry point of include/nghmm.h has a twin nghmm_chain_<name> over a chain of site
-shards; the command line runs all of them on a replica whenever replicate 1 does not win a
+shards, declared there or in another public header under include/ (nghmm_chain_long.h); the command line runs all of them on a replica whenever replicate 1 does not win a
 multi-start run.  So every single-handle function with such a twin must be in replica_util.COVERED,
 and the battery must really call what COVERED names."""
 import importlib
@@ -22,8 +22,15 @@ ALSO = {"nghmm_viterbi", "nghmm_get_posteriors", "nghmm_get_gl", "nghmm_geno_pos
         "nghmm_format_posteriors", "nghmm_lkl_batch"}
 
 
-def _declared(header="nghmm.h"):
-    text = open(os.path.join(ROOT, "include", header)).read()
+def _public_headers():
+    """Every header under include/ but the debugging one: nghmm.h and what declares a twin apart
+    from it (nghmm_chain_long.h)."""
+    return sorted(f for f in os.listdir(os.path.join(ROOT, "include")) if f.endswith(".h") and f != "nghmm_debug.h")
+
+
+def _declared(*headers):
+    headers = headers or _public_headers()
+    text = "".join(open(os.path.join(ROOT, "include", f)).read() for f in headers)
     text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
     text = re.sub(r"//[^\n]*", "", text)
     return set(re.findall(r"\b(nghmm_[a-z_0-9]+)\s*\(", text))
@@ -37,7 +44,7 @@ def test_every_output_entry_point_is_in_the_battery():
     assert {"nghmm_ibd_tracts", "nghmm_sample_paths", "nghmm_tract_support", "nghmm_tract_bounds",
             "nghmm_freq_info", "nghmm_geno_smooth", "nghmm_obs_info", "nghmm_ibd_summary",
             "nghmm_ibd_expect", "nghmm_ibd_moments", "nghmm_ibd_by_length", "nghmm_ibd_longest",
-            "nghmm_ibd_sharing"} <= twins
+            "nghmm_ibd_long", "nghmm_ibd_sharing"} <= twins
     assert ALSO <= names
     missing = sorted((twins | ALSO) - ru.COVERED)
     assert not missing, f"entry points without a replica test (tests/replica_util.py): {missing}"
