@@ -1142,6 +1142,57 @@ int nghmm_chain_ibd_longest(nghmm_t** hs, int n_handles, int what, uint32_t n_le
                             const double* min_length, uint64_t n_regions, const uint64_t* region_begin,
                             const uint64_t* region_end, nghmm_longest_stat* stats);
 
+/* ---- the number of long IBD tracts ----
+ * Per individual, region and threshold L_k the DISTRIBUTION of C_k, the number of IBD runs of the
+ * region whose length is >= L_k (NROH above L_k), exactly, at the handle's CURRENT indF, alpha and
+ * freq.  Everything is nghmm_ibd_longest's unless stated: runs (maximal stretches of z = 1 inside
+ * the region, cut at chromosome starts and at the region's two edges), pi_s, r_s(k, l), rho_s and
+ * blocked steps, Q and W(a, s) = exp(Q_s - Q_a), the thresholds (1 <= K <= 8, in sites or with
+ * NGHMM_COUNT_MB in Mb) and the table b_k(a), regions and their parts per chromosome.
+ *
+ * n_counts = M, 1 <= M <= 16.  Per (individual, region, threshold) the output is M + 1 doubles:
+ * prob[c] = P(C_k = c | y) for c < M and prob[M] = P(C_k >= M | y), each from its own sum, never as
+ * 1 - the rest.  Masses per threshold, over the sites of the region inside one chromosome, for
+ * c = 0 .. M - 1:  N_c: z_s = 0, c long runs so far;  V_c: inside a run that has not reached L_k,
+ * c long runs before it;  R_c (c >= 1): inside a run that has reached L_k, itself counted among the
+ * c;  Top: the absorbed mass with count >= M.
+ *   s = lo:  N_0 = pi_lo(0);  tau_0 = pi_lo(1);  every other mass 0
+ *   s > lo:  tau_c = N_c r_s(0, 1)
+ *            N_c'  = N_c r_s(0, 0) + V_c r_s(1, 0) [+ R_c r_s(1, 0) for c >= 1]
+ *            G_c(s) = sum over starts a >= lo with b_k(a) = s of tau_{a,c} W(a, s)   (oldest first)
+ *            V_c'  = max(V_c rho_s + tau_c - G_c(s), 0)
+ *            R_c'  = R_c rho_s + G_{c-1}(s)            (1 <= c < M)
+ *            Top  += G_{M-1}(s)
+ *   end:     prob[c] = N_c + V_c + R_c  (c < M),   prob[M] = Top
+ * A blocked step discards the ring; a ring entry holds (Q_a, tau_{a,0..M-1}).  The parts of a region
+ * in different chromosomes are independent: the host combines them in site order by a convolution
+ * cut off at M, j ascending, every output from its own sum, the top level absorbing
+ * (top = top_prev + sum over a < M of prev[a] P(part >= M - a)).  With M = 1 the operations are
+ * nghmm_ibd_longest's: prob[0] is its p_none and prob[1] its p_any.  prob[..][c] for c < M does not
+ * depend on M beyond rounding.  A state the data exclude gives exact zeros, and where pi_lo(1) is
+ * exactly 0, N_0 = 1 exactly (the propagated pi_lo(0) carries the roundings of its sum); nothing is
+ * NaN; a part that no window of the threshold fits into (b_k of its first site is none or beyond
+ * it) has no long run: prob[0] = 1 exactly and zeros elsewhere, so a threshold no chromosome reaches
+ * gives exactly that.
+ *
+ * Orders: no float atomics; the same arguments give the same bits on every call, and a region's
+ * record does not depend on which other regions are asked for.  One lane per (individual,
+ * chromosome part of the handle, threshold) in both modes; the backward walk is
+ * nghmm_ibd_longest's.
+ *
+ * NGHMM_ERR_ARG with a message under nghmm_ibd_longest's conditions, and for n_counts outside
+ * 1..16.  Self-contained and read-only exactly like nghmm_ibd_longest: an EM iteration after the
+ * call gives the bits it would have given without it.  Device scratch: nghmm_ibd_longest's, shared
+ * with it (NGHMM_ERR_NOMEM when it cannot be had) -- 40 bytes per cell; per individual
+ * 8 (n_counts + 1) bytes instead of 16 times the sum over the handle's chromosome parts and the
+ * thresholds of the longest window b_k(a) - a + 1 of that threshold in that part; 4 n_lengths bytes
+ * per site for b_k; 8 n_lengths (n_counts + 1) per (individual, region part).  One handle only:
+ * there is no call over a chain of site shards yet.   */
+enum { NGHMM_COUNT_MB = 1 };
+/* prob [I][n_regions][n_lengths][n_counts + 1] (host) */
+int nghmm_ibd_count(nghmm_t* h, int what, uint32_t n_lengths, const double* min_length, uint32_t n_counts,
+                    uint64_t n_regions, const uint64_t* region_begin, const uint64_t* region_end, double* prob);
+
 /* ---- per-site posterior of lying in a long IBD tract ----
  * Per individual, site and threshold L_k the probability P_k(s) that site s lies in an IBD tract
  * of length >= L_k, exactly, at the handle's CURRENT indF, alpha and freq: the track "this site

@@ -10,9 +10,7 @@
 // (implementation of include/nghmm.h; capi_internal.hpp has the handle and the shared helpers.)
 #include <cstddef>
 
-#include "capi_chain.hpp"
-#include "kernels_bounds.hpp"
-#include "kernels_longest.hpp"
+#include "capi_longest_host.hpp"
 
 static_assert(sizeof(nghmm_longest_stat) == 16, "nghmm_longest_stat is 16 bytes");
 static_assert(sizeof(nghmm_longest_stat) == sizeof(LongestRec) &&
@@ -54,91 +52,24 @@ int longest_impl(nghmm_t** hs, int n, int what, uint32_t K, const double* min_le
     return NGHMM_ERR_ARG;
   }
   const bool mb = (what & NGHMM_LONGEST_MB) != 0;
-  if (K < 1 || K > kLongestMaxK || !min_len) {
-    set_error("%s: n_lengths = %u with min_length %s: 1 to %u thresholds are needed", who, K,
-              min_len ? "given" : "NULL", kLongestMaxK);
-    return NGHMM_ERR_ARG;
-  }
-  for (uint32_t k = 0; k < K; ++k) {
-    const double L = min_len[k];
-    const bool ok = std::isfinite(L) && (mb ? L >= 0.0 : (L >= 1.0 && L == std::floor(L))) &&
-                    (k == 0 || L > min_len[k - 1]);
-    if (!ok) {
-      set_error("%s: min_length[%u] = %g: thresholds are finite, strictly increasing and %s", who, k, L,
-                mb ? ">= 0 Mb" : "whole numbers of sites >= 1");
-      return NGHMM_ERR_ARG;
-    }
-  }
+  if ((rc = longest_host::check_lengths(mb, K, min_len, who))) return rc;
   const uint64_t I = hs[0]->I, R = n_regions;
   if ((rc = summary_check_regions(S_tot, I, R, begin, end, stats, nullptr, who))) return rc;
   const bool fast = hs[0]->mode == NGHMM_MODE_FAST;
   if ((rc = chain_check_fast(hs, n, who))) return rc;
-  if (S_tot >= 0xfffffff0ull) {
-    set_error("%s: %llu sites: the table of window ends holds 32-bit site indices", who,
-              (unsigned long long)S_tot);
-    return NGHMM_ERR_ARG;
-  }
-  // the distances of the whole site axis, cum and the chromosomes' edges
+  if ((rc = longest_host::check_site_count(S_tot, who))) return rc;
+  // the distances of the whole site axis, cum and the chromosomes' edges; b_k(a); the regions' parts
+  // per chromosome (capi_longest_host.hpp)
   std::vector<Shard> sh(n);
-  std::vector<double> pos(S_tot), cum(S_tot);
-  {
-    uint64_t base = 0;
-    for (int r = 0; r < n; ++r) {
-      nghmm_t* h = hs[r];
-      if ((rc = use_device(h))) return rc;
-      sh[r].base = base;
-      HIP_TRY(hipMemcpyAsync(pos.data() + base, h->d_pos, h->S * sizeof(double), hipMemcpyDeviceToHost,
-                             h->stream));
-      HIP_TRY(sync_stream(h));
-      base += h->S;
-    }
-  }
-  auto is_start = [&](uint64_t s) { return s == 0 || bounds_chrom_start(pos[s]); };
-  std::vector<uint64_t> chrom_begin(S_tot), chrom_end(S_tot);
-  {
-    double c = 0.0;
-    uint64_t b = 0;
-    for (uint64_t s = 0; s < S_tot; ++s) {
-      if (is_start(s)) b = s;
-      c = is_start(s) ? 0.0 : c + pos[s];
-      cum[s] = c;
-      chrom_begin[s] = b;
-    }
-    uint64_t e = S_tot;
-    for (uint64_t s = S_tot; s-- > 0;) {
-      chrom_end[s] = e;
-      if (is_start(s)) e = s;
-    }
-  }
-  // b_k(a), global: non-decreasing in a inside a chromosome, so two pointers (capi_bylength.hip)
-  std::vector<uint32_t> bt((size_t)K * S_tot);
-  for (uint32_t k = 0; k < K; ++k) {
-    const double L = min_len[k];
-    uint64_t b = 0;
-    for (uint64_t a = 0; a < S_tot; ++a) {
-      const uint64_t e = chrom_end[a];
-      if (b < a) b = a;
-      if (mb) {
-        while (b < e && !(cum[b] - cum[a] >= L)) ++b;
-      } else {
-        // (a whole number of sites beyond the data has no window; the cast of one beyond 2^64 is
-        // not defined)
-        const uint64_t want = a + (L >= (double)S_tot ? S_tot : (uint64_t)L) - 1;
-        b = want < e ? want : e;
-      }
-      bt[(size_t)k * S_tot + a] = b < e ? (uint32_t)b : kLongestNone;
-    }
-  }
-  // the regions' parts per chromosome, in site order
-  std::vector<LongestPart> parts;
-  std::vector<uint64_t> owner;
-  for (uint64_t g = 0; g < R; ++g)
-    for (uint64_t x = begin[g]; x < end[g];) {
-      const uint64_t e = std::min(end[g], chrom_end[x]);
-      parts.push_back(LongestPart{x, e});
-      owner.push_back(g);
-      x = e;
-    }
+  longest_host::Axis ax;
+  if ((rc = longest_host::read_axis(hs, n, S_tot, ax))) return rc;
+  for (int r = 0; r < n; ++r) sh[r].base = ax.base[r];
+  longest_host::window_table(ax, mb, K, min_len);
+  longest_host::region_parts(ax, R, begin, end);
+  auto is_start = [&](uint64_t s) { return ax.is_start(s); };
+  const std::vector<uint32_t>& bt = ax.bt;
+  const std::vector<LongestPart>& parts = ax.parts;
+  const std::vector<uint64_t>& owner = ax.owner;
   const uint64_t P = parts.size();
   // segments, rings and scratch of every shard
   for (int r = 0; r < n; ++r) {
@@ -147,32 +78,8 @@ int longest_impl(nghmm_t** hs, int n, int what, uint32_t K, const double* min_le
     const uint64_t S = h->S;
     if ((rc = use_device(h))) return rc;
     x.cont = r > 0 && !is_start(x.base);
-    for (uint64_t s = 0; s < S; ++s)
-      if (s == 0 || is_start(x.base + s)) x.seg.push_back(s);
-    x.seg.push_back(S);
+    const uint64_t E = longest_host::shard_rings(ax, x.base, S, K, x.seg, x.roff, x.rcap);
     const uint64_t n_seg = x.seg.size() - 1;
-    x.roff.resize(n_seg * K);
-    x.rcap.resize(n_seg * K);
-    uint64_t E = 0;
-    for (uint64_t g = 0; g < n_seg; ++g) {
-      const uint64_t A = x.base + x.seg[g], B = x.base + x.seg[g + 1];
-      for (uint32_t k = 0; k < K; ++k) {
-        const uint32_t* t = bt.data() + (size_t)k * S_tot;
-        uint64_t cap = 1;
-        for (uint64_t a = A; a < B; ++a)
-          if (t[a] != kLongestNone) cap = std::max<uint64_t>(cap, t[a] - a + 1);
-        // the windows that begin in a shard before and reach into the segment (the starts without
-        // a window are the chromosome's last: the ones with a window lie in front of them)
-        for (uint64_t a = A; a-- > chrom_begin[A];) {
-          if (t[a] == kLongestNone) continue;
-          if (t[a] < A) break;
-          cap = std::max<uint64_t>(cap, t[a] - a + 1);
-        }
-        x.roff[g * K + k] = E;
-        x.rcap[g * K + k] = (uint32_t)cap;
-        E += cap;
-      }
-    }
     x.ring_entries = E;
     x.rec.resize((size_t)I * P * K);
     const uint64_t rin_entries = x.cont ? sh[r - 1].ring_entries - sh[r - 1].roff[sh[r - 1].roff.size() - K] : 0;

@@ -47,6 +47,11 @@
 // individual, chromosome or window of N sites and threshold the probability that some IBD run there
 // is of at least that length -- in Mb, or in sites with --longest_sites -- and that none is,
 // exactly, made on the device after the final decode),
+// --ibd_count L1,L2,... [--count_sites] [--count_max M] [--count_window N] (PREFIX.ibd.count: per
+// individual, chromosome or window of N sites and threshold the distribution of the number of IBD
+// runs there of at least that length -- in Mb, or in sites with --count_sites: the probabilities of
+// exactly 0 .. M - 1 and of M or more, M = 8 unless given -- exactly, made on the device after the
+// final decode; one handle only),
 // --ibd_long L1,L2,... [--long_sites] [--long_window N] [--long_thresh P] [--long_post]
 // (PREFIX.ibd.long.regions, PREFIX.ibd.long.sites and, with --long_post, PREFIX.ibd.long.post: per
 // site and threshold the posterior of lying in an IBD tract of at least that length -- in Mb, or
@@ -102,6 +107,8 @@
 #pragma weak nghmm_chain_ibd_longest
 // ... and without the long-tract posterior entry: --ibd_long then stops with a message
 #pragma weak nghmm_chain_ibd_long
+// ... and without the count entry: --ibd_count then stops with a message
+#pragma weak nghmm_ibd_count
 // ... and without the support entries: --ibd_support then stops with a message
 #pragma weak nghmm_tract_support
 #pragma weak nghmm_chain_tract_support
@@ -205,6 +212,14 @@ struct Params {  // ngsF-HMM.hpp:13-52
   // of N sites that restarts at every chromosome start, and per site over the individuals with
   // the count of those at or above --long_thresh; --long_post adds PREFIX.ibd.long.post, the
   // posteriors themselves as raw doubles [K][I][S]; the thresholds are Mb, or sites with --long_sites
+  // --ibd_count L1,L2,...: PREFIX.ibd.count after the final decode (nghmm_ibd_count): per threshold
+  // the distribution of the number of IBD runs of at least that length, count_max + 1 probabilities,
+  // per individual and chromosome, or with --count_window N per window of N sites that restarts at
+  // every chromosome start; the thresholds are Mb, or sites with --count_sites
+  bool ibd_count = false, count_sites = false;
+  std::vector<double> count_len;
+  uint64_t count_window = 0;
+  long long count_max = 0;   // 0: not given (8)
   bool ibd_long = false, long_sites = false, long_post = false;
   std::vector<double> long_len;
   uint64_t long_window = 0;
@@ -1801,6 +1816,55 @@ void write_ibd_longest(const Params& P, Cohort& C) {
   if (fclose(fh) != 0) fatal(__FUNCTION__, "cannot write the longest-tract output file!");
 }
 
+// PREFIX.ibd.count: a header line, then per individual, region and threshold "ind chr first_pos
+// last_pos n_sites min_len p_0 .. p_{M-1} p_ge_M" (tab-separated, ordered by individual, then region,
+// then threshold; IDs, chromosome names, positions and regions as --ibd_longest writes them, with
+// --count_window for the windows): the probabilities that exactly 0 .. M - 1 IBD runs of the region
+// are of at least min_len (Mb, or sites with --count_sites) and that M or more are.  Doubles as
+// %.10g; everything conditional on the final indF, alpha and frequencies.  One handle.
+void write_ibd_count(const Params& P, Cohort& C) {
+  if (!nghmm_ibd_count) fatal(__FUNCTION__, "--ibd_count: the library has no nghmm_ibd_count!");
+  if (C.n() != 1) fatal(__FUNCTION__, "--ibd_count: site shards (--n_gpus > 1) are not supported yet!");
+  const uint64_t I = P.n_ind, S = P.n_sites, K = P.count_len.size();
+  const uint64_t M = P.count_max ? (uint64_t)P.count_max : 8;
+  std::vector<uint64_t> begin, end;
+  std::vector<size_t> chrom;   // the chromosome run of every region
+  for (size_t c = 0; c < P.chrom_first.size(); c++) {
+    const uint64_t a = P.chrom_first[c], b = c + 1 < P.chrom_first.size() ? P.chrom_first[c + 1] : S;
+    const uint64_t w = P.count_window ? P.count_window : b - a;
+    for (uint64_t lo = a; lo < b; lo += w) {
+      begin.push_back(lo);
+      end.push_back(b - lo < w ? b : lo + w);
+      chrom.push_back(c);
+    }
+  }
+  const uint64_t R = begin.size();
+  std::vector<double> pr((size_t)I * R * K * (M + 1));
+  check(nghmm_ibd_count(C.hs[0], P.count_sites ? 0 : NGHMM_COUNT_MB, (uint32_t)K, P.count_len.data(), (uint32_t)M,
+                        R, begin.data(), end.data(), pr.data()),
+        "ibd_count");
+  const std::string name = P.prefix + ".ibd.count";
+  FILE* fh = fopen(name.c_str(), "w");
+  if (!fh) fatal(__FUNCTION__, "cannot open count output file!");
+  setvbuf(fh, nullptr, _IOFBF, 1 << 22);
+  fputs("ind\tchr\tfirst_pos\tlast_pos\tn_sites\tmin_len", fh);
+  for (uint64_t c = 0; c < M; c++) fprintf(fh, "\tp_%llu", (unsigned long long)c);
+  fprintf(fh, "\tp_ge_%llu\n", (unsigned long long)M);
+  for (uint64_t i = 0; i < I; i++) {
+    const std::string id = P.ind_names.empty() ? "ind" + std::to_string(i) : P.ind_names[i];
+    for (uint64_t r = 0; r < R; r++)
+      for (uint64_t k = 0; k < K; k++) {
+        const double* t = pr.data() + ((i * R + r) * K + k) * (M + 1);
+        fprintf(fh, "%s\t%s\t%llu\t%llu\t%llu\t%.10g", id.c_str(), P.chrom_name[chrom[r]].c_str(),
+                (unsigned long long)P.site_pos[begin[r]], (unsigned long long)P.site_pos[end[r] - 1],
+                (unsigned long long)(end[r] - begin[r]), P.count_len[k]);
+        for (uint64_t c = 0; c <= M; c++) fprintf(fh, "\t%.10g", t[c]);
+        fputc('\n', fh);
+      }
+  }
+  if (fclose(fh) != 0) fatal(__FUNCTION__, "cannot write the count output file!");
+}
+
 // PREFIX.ibd.long.regions: a header line, then per individual, region and threshold "ind chr
 // first_pos last_pos n_sites min_len exp_sites exp_mb" (tab-separated; IDs, regions and order as
 // --ibd_by_length writes them, with --long_window for the windows): the expected sites and Mb of
@@ -2206,6 +2270,8 @@ void parse_cmd_args(Params& P, int argc, char** argv) {  // parse_args.cpp:41-22
       {"ibd_long", required_argument, nullptr, 1040}, {"long_sites", no_argument, nullptr, 1041},
       {"long_window", required_argument, nullptr, 1042}, {"long_thresh", required_argument, nullptr, 1043},
       {"long_post", no_argument, nullptr, 1044},
+      {"ibd_count", required_argument, nullptr, 1045}, {"count_sites", no_argument, nullptr, 1046},
+      {"count_window", required_argument, nullptr, 1047}, {"count_max", required_argument, nullptr, 1048},
       {0, 0, 0, 0}};
   long taus_kat = 0;
   bool parse_kat = false, se_kat = false;
@@ -2312,6 +2378,30 @@ void parse_cmd_args(Params& P, int argc, char** argv) {  // parse_args.cpp:41-22
       case 1039:
         if (atoll(optarg) < 1) fatal(__FUNCTION__, "invalid --longest_window (sites per window)!");
         P.longest_window = strtoull(optarg, nullptr, 10);
+        break;
+      case 1045: {   // L1,L2,...: every field a number; the rest is checked once the unit is known
+        P.ibd_count = true;
+        P.count_len.clear();
+        const char* q = optarg;
+        while (true) {
+          char* e = nullptr;
+          const double v = strtod(q, &e);
+          if (e == q || (*e != ',' && *e != '\0'))
+            fatal(__FUNCTION__, "invalid --ibd_count (a comma-separated list of minimum lengths)!");
+          P.count_len.push_back(v);
+          if (*e == '\0') break;
+          q = e + 1;
+        }
+        break;
+      }
+      case 1046: P.count_sites = true; break;
+      case 1047:
+        if (atoll(optarg) < 1) fatal(__FUNCTION__, "invalid --count_window (sites per window)!");
+        P.count_window = strtoull(optarg, nullptr, 10);
+        break;
+      case 1048:
+        if (atoll(optarg) < 1 || atoll(optarg) > 16) fatal(__FUNCTION__, "invalid --count_max (1 to 16 count levels)!");
+        P.count_max = atoll(optarg);
         break;
       case 1040: {   // L1,L2,...: every field a number; the rest is checked once the unit is known
         P.ibd_long = true;
@@ -2527,6 +2617,22 @@ void parse_cmd_args(Params& P, int argc, char** argv) {  // parse_args.cpp:41-22
   }
   if (!P.ibd_long && (P.long_window || P.long_sites || P.long_post))
     warn(__FUNCTION__, "--long_window, --long_sites, --long_thresh and --long_post are only used by --ibd_long");
+  if (P.ibd_count) {
+    if (!nghmm_ibd_count) fatal(__FUNCTION__, "--ibd_count: the library has no nghmm_ibd_count!");
+    if (P.count_len.empty() || P.count_len.size() > 8)
+      fatal(__FUNCTION__, "invalid --ibd_count (1 to 8 minimum lengths)!");
+    for (size_t k = 0; k < P.count_len.size(); k++) {
+      const double v = P.count_len[k];
+      const bool ok = std::isfinite(v) && (P.count_sites ? (v >= 1 && v == std::floor(v)) : v >= 0) &&
+                      (k == 0 || v > P.count_len[k - 1]);
+      if (!ok)
+        fatal(__FUNCTION__, P.count_sites
+                                ? "invalid --ibd_count (strictly increasing whole numbers of sites >= 1)!"
+                                : "invalid --ibd_count (strictly increasing lengths in Mb >= 0)!");
+    }
+  }
+  if (!P.ibd_count && (P.count_window || P.count_sites || P.count_max))
+    warn(__FUNCTION__, "--count_window, --count_sites and --count_max are only used by --ibd_count");
   if (P.min_iters < 1 || P.max_iters < 1 || P.min_iters >= P.max_iters)
     fatal(__FUNCTION__, "invalid number of iterations!");
   if (P.n_threads < 1) fatal(__FUNCTION__, "invalid number of threads!");
@@ -2541,6 +2647,8 @@ void parse_cmd_args(Params& P, int argc, char** argv) {  // parse_args.cpp:41-22
       fatal(__FUNCTION__, "too few sites for --n_gpus (the site axis is what the GPUs share)!");
     if (P.mode != NGHMM_MODE_FAST) fatal(__FUNCTION__, "--n_gpus > 1 needs --mode fast!");
     if (P.n_starts > 1) fatal(__FUNCTION__, "--n_starts and --n_gpus > 1 cannot be combined!");
+    if (P.ibd_count)
+      fatal(__FUNCTION__, "--ibd_count: site shards (--n_gpus > 1) are not supported yet!");
   }
   if (P.in_ind_names) {  // the first tab- or space-separated field of each line (convert_ibd.pl --ind)
     gzFile fh = gzopen(P.in_ind_names, "r");
@@ -2560,8 +2668,8 @@ void parse_cmd_args(Params& P, int argc, char** argv) {  // parse_args.cpp:41-22
       fatal(__FUNCTION__, "number of lines in --ind_names file is not --n_ind!");
     if (!P.ibd_bed && !P.sample_paths && !P.indF_se && !P.ibd_summary && !P.ibd_sharing && !P.ibd_support &&
         !P.ibd_bounds && !P.geno_summary && !P.ibd_expect && !P.ibd_moments && !P.ibd_by_length &&
-        !P.ibd_longest && !P.ibd_long)
-      warn(__FUNCTION__, "--ind_names is only used by --ibd_bed, --sample_paths, --indF_se, --ibd_summary, --ibd_sharing, --ibd_support, --ibd_bounds, --geno_summary, --ibd_expect, --ibd_moments, --ibd_by_length, --ibd_longest and --ibd_long");
+        !P.ibd_longest && !P.ibd_long && !P.ibd_count)
+      warn(__FUNCTION__, "--ind_names is only used by --ibd_bed, --sample_paths, --indF_se, --ibd_summary, --ibd_sharing, --ibd_support, --ibd_bounds, --geno_summary, --ibd_expect, --ibd_moments, --ibd_by_length, --ibd_longest, --ibd_long and --ibd_count");
   }
   P.prefix = P.out_prefix;
 }
@@ -2667,6 +2775,7 @@ void finish_run(Params& P, Cohort& C) {
   if (P.ibd_by_length) write_ibd_by_length(P, C);
   if (P.ibd_longest) write_ibd_longest(P, C);
   if (P.ibd_long) write_ibd_long(P, C);
+  if (P.ibd_count) write_ibd_count(P, C);
   if (P.verbose >= 2)  // (not a line of the reference's)
     fprintf(P.out, "> decoded in %.2f s, output files written in %.2f s\n", t1 - t0, omp_get_wtime() - t1);
 }
@@ -2792,6 +2901,7 @@ int main(int argc, char** argv) {
         runs[r].ibd_by_length = P.ibd_by_length && r == best;
         runs[r].ibd_longest = P.ibd_longest && r == best;
         runs[r].ibd_long = P.ibd_long && r == best;
+        runs[r].ibd_count = P.ibd_count && r == best;
         finish_run(runs[r], cs[r]);
       }
       fclose(runs[r].out);
@@ -2829,6 +2939,7 @@ int main(int argc, char** argv) {
         exts.push_back(".ibd.long.sites");
         if (P.long_post) exts.push_back(".ibd.long.post");
       }
+      if (P.ibd_count) exts.push_back(".ibd.count");
       for (unsigned k = 1; P.sample_paths && k <= P.sample_keep; k++) {
         char tag[32];
         snprintf(tag, sizeof tag, ".sample_%02u.ibd", k);

@@ -177,6 +177,7 @@ def load_library():
         "nghmm_ibd_longest": (i32, [vp, i32, u32, dp, u64, C.POINTER(u64), C.POINTER(u64), vp]),
         "nghmm_chain_ibd_longest": (i32, [C.POINTER(vp), i32, i32, u32, dp, u64, C.POINTER(u64),
                                           C.POINTER(u64), vp]),
+        "nghmm_ibd_count": (i32, [vp, i32, u32, dp, u32, u64, C.POINTER(u64), C.POINTER(u64), dp]),
         "nghmm_ibd_long": (i32, [vp, i32, u32, dp, d, u64, C.POINTER(u64), C.POINTER(u64), vp, vp, dp]),
         "nghmm_chain_ibd_long": (i32, [C.POINTER(vp), i32, i32, u32, dp, d, u64, C.POINTER(u64),
                                        C.POINTER(u64), vp, vp, dp]),
@@ -229,6 +230,7 @@ EXPORTED_SYMBOLS = [
     "nghmm_ibd_by_length", "nghmm_chain_ibd_by_length", "nghmm_debug_bylength_qmax",
     "nghmm_ibd_longest", "nghmm_chain_ibd_longest",
     "nghmm_ibd_long",
+    "nghmm_ibd_count",
 ]
 # (nghmm_chain_ibd_long is declared in include/nghmm_chain_long.h)
 
@@ -813,6 +815,30 @@ class LongestStat(C.Structure):      # nghmm_longest_stat (include/nghmm.h)
 
 LONGEST_DTYPE = np.dtype([(n, np.float64) for n, _ in LongestStat._fields_])
 assert LONGEST_DTYPE.itemsize == C.sizeof(LongestStat) == 16
+
+
+COUNT_MB = 1           # nghmm_ibd_count: thresholds in Mb instead of sites
+COUNT_MAX = 16         # nghmm_ibd_count: the largest n_counts
+
+
+def count_summary(prob, levels=(0.025, 0.5, 0.975)):
+    """ibd_count's records [..][M + 1] in short: a dict of
+    mean_lower [..]  sum of c p_c + M p_M: a lower bound of E[C], equal to it where prob[..., M] is 0;
+    p_more [..]      prob[..., M], the probability of M runs or more;
+    mode [..]        the most probable count (the first of equals; M stands for "M or more");
+    quantiles [..][len(levels)]  integers: the smallest c whose cumulative probability reaches the
+                     level, M meaning "M or more" (censored)."""
+    p = np.asarray(prob, dtype=np.float64)
+    if p.ndim < 1 or p.shape[-1] < 2:
+        raise NgsFHMMError(-10, "count_summary: prob is [..][M + 1] with M >= 1")
+    lv = np.atleast_1d(np.asarray(levels, dtype=np.float64))
+    if lv.ndim != 1 or not ((lv >= 0) & (lv <= 1)).all():
+        raise NgsFHMMError(-10, "count_summary: levels lie in [0, 1]")
+    M = p.shape[-1] - 1
+    cum = np.cumsum(p[..., :M], axis=-1)
+    q = (cum[..., None, :] < lv[:, None]).sum(axis=-1).astype(np.int64)
+    return {"mean_lower": (p * np.arange(M + 1)).sum(axis=-1), "p_more": p[..., M].copy(),
+            "mode": np.argmax(p, axis=-1).astype(np.int64), "quantiles": q}
 
 
 LONG_MB = 1            # nghmm_ibd_long: thresholds in Mb instead of sites
@@ -1469,6 +1495,27 @@ class NgsFHMM:
         return _ibd_by_length(lambda *a: self.lib.nghmm_ibd_longest(self._h, *a), self._check,
                               self.n_ind, self.n_sites, min_len, unit, regions, LONGEST_DTYPE,
                               "ibd_longest", LONGEST_MB)
+
+    def ibd_count(self, min_len, unit="sites", regions=None, max_count=8):
+        """The distribution of the number of long IBD runs, exactly (nghmm_ibd_count): a float64
+        array [I][R][K][max_count + 1] -- per individual, region and threshold the probabilities
+        that exactly 0, 1, .., max_count - 1 IBD runs of the region are of at least min_len[k]
+        (sites, or Mb with unit="mb"), and last that max_count or more are; each from its own sum.
+        Arguments as ibd_longest; 1 <= max_count <= 16.  count_summary gives mean, mode and
+        quantiles."""
+        u64p = C.POINTER(C.c_uint64)
+        L, reg = _by_length_args(self.n_sites, min_len, unit, regions, "ibd_count")
+        if isinstance(max_count, bool) or not isinstance(max_count, (int, np.integer)) or \
+                not 0 <= int(max_count) < 2 ** 32:
+            raise NgsFHMMError(-10, "ibd_count: max_count is a whole number from 1 to 16")
+        R, K, M = len(reg), len(L), int(max_count)
+        begin, end = np.ascontiguousarray(reg[:, 0]), np.ascontiguousarray(reg[:, 1])
+        prob = np.zeros((self.n_ind, R, K, M + 1))
+        self._check(self.lib.nghmm_ibd_count(self._h, COUNT_MB if unit == "mb" else 0, K, _dp(L) if K else None,
+                                             M, R, begin.ctypes.data_as(u64p) if R else None,
+                                             end.ctypes.data_as(u64p) if R else None,
+                                             _dp(prob) if R and K else None))
+        return prob
 
     def ibd_long(self, min_len, unit="sites", regions=None, sites=True, post=False, threshold=0.5):
         """The posterior of every site of lying in an IBD tract of at least min_len[k], exactly
