@@ -1193,6 +1193,73 @@ enum { NGHMM_COUNT_MB = 1 };
 int nghmm_ibd_count(nghmm_t* h, int what, uint32_t n_lengths, const double* min_length, uint32_t n_counts,
                     uint64_t n_regions, const uint64_t* region_begin, const uint64_t* region_end, double* prob);
 
+/* ---- mean and variance of IBD in long tracts ----
+ * Per individual, region and threshold L_k the posterior mean and covariance matrix of
+ *   A_k = the total length of the region's IBD runs whose length is >= L_k   (F_ROH above L_k)
+ *   C_k = their number                                                         (NROH above L_k)
+ * exactly, at the handle's CURRENT indF, alpha and freq.  Everything is nghmm_ibd_count's unless
+ * stated: runs (maximal stretches of z = 1 inside the region, cut at chromosome starts and at the
+ * region's two edges), regions and their parts per chromosome, pi_s, r_s(k, l), rho_s and blocked
+ * steps, Q and W(a, s) = exp(Q_s - Q_a), the thresholds (1 <= K <= 8, in sites or with
+ * NGHMM_LONG_MOMENTS_MB in Mb) and the table b_k(a).  The length of a run a..b is len(a, b) =
+ * b - a + 1 in sites and cum_b - cum_a in Mb, as nghmm_ibd_by_length measures it.
+ *
+ * Per threshold over the sites of one part (one chromosome's share of a region, first site lo)
+ * every mass class X in {N, V, R} is a vector of six doubles: the mass and the moments of
+ * (A - oA, C - oC) on it in the order (1, A, C, A^2, AC, C^2); (oA, oC) is the lane's offset pair,
+ * (0, 0) at lo.  N: z_s = 0;  V: inside a run that has not reached L_k;  R: inside a run that has
+ * reached L_k and is counted.  Sh(m; l, c), the moments of (A + l, C + c):
+ *   m0' = m0;  mA' = mA + l m0;  mC' = mC + c m0;  mAA' = mAA + 2 l mA + l^2 m0;
+ *   mAC' = mAC + l mC + c mA + l c m0;  mCC' = mCC + 2 c mC + c^2 m0
+ *   s = lo:  N = (pi_lo(0), 0, ..) (mass 1 exactly where pi_lo(1) == 0, as nghmm_ibd_count);
+ *            tau = (pi_lo(1), 0, ..);  V = R = 0
+ *   s > lo:  tau = N r_s(0, 1);   N' = N r_s(0, 0) + V r_s(1, 0) + R r_s(1, 0)
+ *   for each start a with b_k(a) = s, oldest first:
+ *            g_a = Sh(tau_a W(a, s); oA_a - oA, oC_a - oC)   (the entry at the lane's current offsets)
+ *            G += g_a;   Gs += Sh(g_a; len(a, s), 1)
+ *   V' = V rho_s + tau - G component-wise; the whole vector is 0 if its mass is <= 0
+ *   R' = Sh(R rho_s; delta_s, 0) + Gs,   delta_s = 1 in sites and d_s in Mb
+ * A ring entry holds (Q_a, oA_a, oC_a, tau_a[6]); a blocked step discards the ring.  After the
+ * update at every site with (s - lo) % 8 == 7 the vectors are re-centred: with t = (N + V) + R,
+ * dA = t_A / t_0 and dC = t_C / t_0:  X <- Sh(X; -dA, -dC) for N, V, R;  oA += dA;  oC += dC.  (The
+ * raw moments would lose E[A]^2 / Var(A) digits when they are closed; the centred ones do not.)
+ * At the end of the part, with t as above, m0 = t_0, muA = t_A / m0 and muC = t_C / m0:
+ *   mean_a = oA + muA;   mean_t = oC + muC;   var_a = max(t_AA / m0 - muA^2, 0);
+ *   cov_at = t_AC / m0 - muA muC;   var_t = max(t_CC / m0 - muC^2, 0)
+ * A part that no window of the threshold fits into gives five exact zeros.  Chromosomes are
+ * independent given the parameters: the host adds a region's parts in site order, all five fields.
+ * Everything is conditional on indF, alpha and the allele frequencies, as nghmm_ibd_moments.  At
+ * L = 1 site (and 0 Mb) over whole chromosomes the record is nghmm_ibd_moments'; over whole
+ * chromosomes mean_t is nghmm_ibd_by_length's tracts and mean_a its length; mean_t and var_t are
+ * the mean and variance of nghmm_ibd_count's distribution.  A state the data exclude gives exact
+ * zeros; nothing is ever NaN.
+ *
+ * Orders: no float atomics; the same arguments give the same bits on every call, and a record does
+ * not depend on which other regions or thresholds are asked for.  One lane per (individual,
+ * chromosome part of the handle, threshold) in both modes; the backward walk is nghmm_ibd_longest's.
+ *
+ * NGHMM_ERR_ARG with a message under nghmm_ibd_count's conditions.  Self-contained and read-only
+ * exactly like it: an EM iteration after the call gives the bits it would have given without it.
+ * Device scratch: nghmm_ibd_longest's, shared with it (NGHMM_ERR_NOMEM when it cannot be had) --
+ * 40 bytes per cell; per individual 72 bytes times the sum over the handle's chromosome parts and
+ * the thresholds of the longest window b_k(a) - a + 1 of that threshold in that part;
+ * 4 n_lengths + 16 bytes per site; 40 n_lengths per (individual, region part).  One handle only:
+ * there is no call over a chain of site shards.   */
+enum { NGHMM_LONG_MOMENTS_MB = 1 };
+typedef struct nghmm_long_moment_stat {  /* 40 bytes; one per (individual, region, threshold) */
+  double mean_a;  /* E[A_k | y]: expected sites (or Mb) of the region inside runs of length >= L_k */
+  double mean_t;  /* E[C_k | y]: expected number of such runs */
+  double var_a;   /* Var(A_k | y), >= 0 */
+  double cov_at;  /* Cov(A_k, C_k | y) */
+  double var_t;   /* Var(C_k | y), >= 0 */
+} nghmm_long_moment_stat;
+#ifdef __cplusplus
+static_assert(sizeof(nghmm_long_moment_stat) == 40, "record size");
+#endif
+/* stats [I][n_regions][n_lengths] (host) */
+int nghmm_ibd_long_moments(nghmm_t* h, int what, uint32_t n_lengths, const double* min_length, uint64_t n_regions,
+                           const uint64_t* region_begin, const uint64_t* region_end, nghmm_long_moment_stat* stats);
+
 /* ---- per-site posterior of lying in a long IBD tract ----
  * Per individual, site and threshold L_k the probability P_k(s) that site s lies in an IBD tract
  * of length >= L_k, exactly, at the handle's CURRENT indF, alpha and freq: the track "this site

@@ -27,7 +27,8 @@ from .hmm import (NgsFHMM, NgsFHMMError, Group, Chain, MODE_EXACT, MODE_FAST, GE
                   MOMENTS_MB, MOMENT_REGION_DTYPE, moment_sd,
                   BYLENGTH_MB, BYLENGTH_DTYPE, by_length_classes,
                   LONG_MB, LONG_REGION_DTYPE, LONG_SITE_DTYPE, long_tracts,
-                  LONGEST_MB, LONGEST_DTYPE, longest_classes, COUNT_MB, count_summary)
+                  LONGEST_MB, LONGEST_DTYPE, longest_classes, COUNT_MB, count_summary,
+                  LONG_MOMENTS_MB, LONG_MOMENT_DTYPE, long_moment_sd)
 from . import simulate
 
 __all__ = ["NgsFHMM", "NgsFHMMError", "Group", "Chain", "MODE_EXACT", "MODE_FAST", "GENO_PACKED", "LD_INTENDED", "EPROB_LD", "library_path",
@@ -42,4 +43,5 @@ __all__ = ["NgsFHMM", "NgsFHMMError", "Group", "Chain", "MODE_EXACT", "MODE_FAST
            "EXPECT_SITE_DTYPE", "expect_tract_length", "MOMENTS_MB", "MOMENT_REGION_DTYPE",
            "moment_sd", "BYLENGTH_MB", "BYLENGTH_DTYPE", "by_length_classes",
            "LONG_MB", "LONG_REGION_DTYPE", "LONG_SITE_DTYPE", "long_tracts",
-           "LONGEST_MB", "LONGEST_DTYPE", "longest_classes", "COUNT_MB", "count_summary"]
+           "LONGEST_MB", "LONGEST_DTYPE", "longest_classes", "COUNT_MB", "count_summary",
+           "LONG_MOMENTS_MB", "LONG_MOMENT_DTYPE", "long_moment_sd"]

@@ -52,6 +52,11 @@
 // runs there of at least that length -- in Mb, or in sites with --count_sites: the probabilities of
 // exactly 0 .. M - 1 and of M or more, M = 8 unless given -- exactly, made on the device after the
 // final decode; one handle only),
+// --ibd_long_moments L1,L2,... [--long_moments_sites] [--long_moments_window N]
+// (PREFIX.ibd.long.moments: per individual, chromosome or window of N sites and threshold the
+// posterior mean and standard deviation of the total length inside IBD runs there of at least that
+// length and of their number, and the correlation of the two -- in Mb, or in sites with
+// --long_moments_sites -- exactly, made on the device after the final decode; one handle only),
 // --ibd_long L1,L2,... [--long_sites] [--long_window N] [--long_thresh P] [--long_post]
 // (PREFIX.ibd.long.regions, PREFIX.ibd.long.sites and, with --long_post, PREFIX.ibd.long.post: per
 // site and threshold the posterior of lying in an IBD tract of at least that length -- in Mb, or
@@ -109,6 +114,8 @@
 #pragma weak nghmm_chain_ibd_long
 // ... and without the count entry: --ibd_count then stops with a message
 #pragma weak nghmm_ibd_count
+// ... and without the long-tract moments entry: --ibd_long_moments then stops with a message
+#pragma weak nghmm_ibd_long_moments
 // ... and without the support entries: --ibd_support then stops with a message
 #pragma weak nghmm_tract_support
 #pragma weak nghmm_chain_tract_support
@@ -220,6 +227,14 @@ struct Params {  // ngsF-HMM.hpp:13-52
   std::vector<double> count_len;
   uint64_t count_window = 0;
   long long count_max = 0;   // 0: not given (8)
+  // --ibd_long_moments L1,L2,...: PREFIX.ibd.long.moments after the final decode
+  // (nghmm_ibd_long_moments): per threshold the mean and sd of the total length inside IBD runs of at
+  // least that length and of their number, and their correlation, per individual and chromosome, or
+  // with --long_moments_window N per window of N sites that restarts at every chromosome start; the
+  // thresholds are Mb, or sites with --long_moments_sites
+  bool ibd_long_moments = false, long_moments_sites = false;
+  std::vector<double> long_moments_len;
+  uint64_t long_moments_window = 0;
   bool ibd_long = false, long_sites = false, long_post = false;
   std::vector<double> long_len;
   uint64_t long_window = 0;
@@ -1865,6 +1880,56 @@ void write_ibd_count(const Params& P, Cohort& C) {
   if (fclose(fh) != 0) fatal(__FUNCTION__, "cannot write the count output file!");
 }
 
+// PREFIX.ibd.long.moments: a header line, then per individual, region and threshold "ind chr
+// first_pos last_pos n_sites min_len exp_len sd_len exp_tracts sd_tracts corr" (tab-separated; lines,
+// IDs and order as --ibd_count writes them, with --long_moments_window for the windows): the
+// posterior mean and standard deviation of the total length inside the region's IBD runs of at least
+// min_len (Mb, or sites with --long_moments_sites) and of the number of those runs, and the
+// correlation of the two, NA where a variance is 0.  Doubles as %.10g; everything conditional on
+// the final indF, alpha and frequencies.  One handle.
+void write_ibd_long_moments(const Params& P, Cohort& C) {
+  if (!nghmm_ibd_long_moments)
+    fatal(__FUNCTION__, "--ibd_long_moments: the library has no nghmm_ibd_long_moments!");
+  if (C.n() != 1) fatal(__FUNCTION__, "--ibd_long_moments: site shards (--n_gpus > 1) are not supported yet!");
+  const uint64_t I = P.n_ind, S = P.n_sites, K = P.long_moments_len.size();
+  std::vector<uint64_t> begin, end;
+  std::vector<size_t> chrom;   // the chromosome run of every region
+  for (size_t c = 0; c < P.chrom_first.size(); c++) {
+    const uint64_t a = P.chrom_first[c], b = c + 1 < P.chrom_first.size() ? P.chrom_first[c + 1] : S;
+    const uint64_t w = P.long_moments_window ? P.long_moments_window : b - a;
+    for (uint64_t lo = a; lo < b; lo += w) {
+      begin.push_back(lo);
+      end.push_back(b - lo < w ? b : lo + w);
+      chrom.push_back(c);
+    }
+  }
+  const uint64_t R = begin.size();
+  std::vector<nghmm_long_moment_stat> st((size_t)I * R * K);
+  check(nghmm_ibd_long_moments(C.hs[0], P.long_moments_sites ? 0 : NGHMM_LONG_MOMENTS_MB, (uint32_t)K,
+                               P.long_moments_len.data(), R, begin.data(), end.data(), st.data()),
+        "ibd_long_moments");
+  const std::string name = P.prefix + ".ibd.long.moments";
+  FILE* fh = fopen(name.c_str(), "w");
+  if (!fh) fatal(__FUNCTION__, "cannot open long-tract moments output file!");
+  setvbuf(fh, nullptr, _IOFBF, 1 << 22);
+  fputs("ind\tchr\tfirst_pos\tlast_pos\tn_sites\tmin_len\texp_len\tsd_len\texp_tracts\tsd_tracts\tcorr\n", fh);
+  for (uint64_t i = 0; i < I; i++) {
+    const std::string id = P.ind_names.empty() ? "ind" + std::to_string(i) : P.ind_names[i];
+    for (uint64_t r = 0; r < R; r++)
+      for (uint64_t k = 0; k < K; k++) {
+        const nghmm_long_moment_stat& t = st[(i * R + r) * K + k];
+        const double sd_a = std::sqrt(t.var_a > 0 ? t.var_a : 0.0), sd_t = std::sqrt(t.var_t > 0 ? t.var_t : 0.0);
+        fprintf(fh, "%s\t%s\t%llu\t%llu\t%llu\t%.10g\t%.10g\t%.10g\t%.10g\t%.10g\t", id.c_str(),
+                P.chrom_name[chrom[r]].c_str(), (unsigned long long)P.site_pos[begin[r]],
+                (unsigned long long)P.site_pos[end[r] - 1], (unsigned long long)(end[r] - begin[r]),
+                P.long_moments_len[k], t.mean_a, sd_a, t.mean_t, sd_t);
+        if (t.var_a > 0 && t.var_t > 0) fprintf(fh, "%.10g\n", t.cov_at / (sd_a * sd_t));
+        else fputs("NA\n", fh);
+      }
+  }
+  if (fclose(fh) != 0) fatal(__FUNCTION__, "cannot write the long-tract moments output file!");
+}
+
 // PREFIX.ibd.long.regions: a header line, then per individual, region and threshold "ind chr
 // first_pos last_pos n_sites min_len exp_sites exp_mb" (tab-separated; IDs, regions and order as
 // --ibd_by_length writes them, with --long_window for the windows): the expected sites and Mb of
@@ -2272,6 +2337,8 @@ void parse_cmd_args(Params& P, int argc, char** argv) {  // parse_args.cpp:41-22
       {"long_post", no_argument, nullptr, 1044},
       {"ibd_count", required_argument, nullptr, 1045}, {"count_sites", no_argument, nullptr, 1046},
       {"count_window", required_argument, nullptr, 1047}, {"count_max", required_argument, nullptr, 1048},
+      {"ibd_long_moments", required_argument, nullptr, 1049}, {"long_moments_sites", no_argument, nullptr, 1050},
+      {"long_moments_window", required_argument, nullptr, 1051},
       {0, 0, 0, 0}};
   long taus_kat = 0;
   bool parse_kat = false, se_kat = false;
@@ -2402,6 +2469,26 @@ void parse_cmd_args(Params& P, int argc, char** argv) {  // parse_args.cpp:41-22
       case 1048:
         if (atoll(optarg) < 1 || atoll(optarg) > 16) fatal(__FUNCTION__, "invalid --count_max (1 to 16 count levels)!");
         P.count_max = atoll(optarg);
+        break;
+      case 1049: {   // L1,L2,...: every field a number; the rest is checked once the unit is known
+        P.ibd_long_moments = true;
+        P.long_moments_len.clear();
+        const char* q = optarg;
+        while (true) {
+          char* e = nullptr;
+          const double v = strtod(q, &e);
+          if (e == q || (*e != ',' && *e != '\0'))
+            fatal(__FUNCTION__, "invalid --ibd_long_moments (a comma-separated list of minimum lengths)!");
+          P.long_moments_len.push_back(v);
+          if (*e == '\0') break;
+          q = e + 1;
+        }
+        break;
+      }
+      case 1050: P.long_moments_sites = true; break;
+      case 1051:
+        if (atoll(optarg) < 1) fatal(__FUNCTION__, "invalid --long_moments_window (sites per window)!");
+        P.long_moments_window = strtoull(optarg, nullptr, 10);
         break;
       case 1040: {   // L1,L2,...: every field a number; the rest is checked once the unit is known
         P.ibd_long = true;
@@ -2633,6 +2720,23 @@ void parse_cmd_args(Params& P, int argc, char** argv) {  // parse_args.cpp:41-22
   }
   if (!P.ibd_count && (P.count_window || P.count_sites || P.count_max))
     warn(__FUNCTION__, "--count_window, --count_sites and --count_max are only used by --ibd_count");
+  if (P.ibd_long_moments) {
+    if (!nghmm_ibd_long_moments)
+      fatal(__FUNCTION__, "--ibd_long_moments: the library has no nghmm_ibd_long_moments!");
+    if (P.long_moments_len.empty() || P.long_moments_len.size() > 8)
+      fatal(__FUNCTION__, "invalid --ibd_long_moments (1 to 8 minimum lengths)!");
+    for (size_t k = 0; k < P.long_moments_len.size(); k++) {
+      const double v = P.long_moments_len[k];
+      const bool ok = std::isfinite(v) && (P.long_moments_sites ? (v >= 1 && v == std::floor(v)) : v >= 0) &&
+                      (k == 0 || v > P.long_moments_len[k - 1]);
+      if (!ok)
+        fatal(__FUNCTION__, P.long_moments_sites
+                                ? "invalid --ibd_long_moments (strictly increasing whole numbers of sites >= 1)!"
+                                : "invalid --ibd_long_moments (strictly increasing lengths in Mb >= 0)!");
+    }
+  }
+  if (!P.ibd_long_moments && (P.long_moments_window || P.long_moments_sites))
+    warn(__FUNCTION__, "--long_moments_window and --long_moments_sites are only used by --ibd_long_moments");
   if (P.min_iters < 1 || P.max_iters < 1 || P.min_iters >= P.max_iters)
     fatal(__FUNCTION__, "invalid number of iterations!");
   if (P.n_threads < 1) fatal(__FUNCTION__, "invalid number of threads!");
@@ -2649,6 +2753,8 @@ void parse_cmd_args(Params& P, int argc, char** argv) {  // parse_args.cpp:41-22
     if (P.n_starts > 1) fatal(__FUNCTION__, "--n_starts and --n_gpus > 1 cannot be combined!");
     if (P.ibd_count)
       fatal(__FUNCTION__, "--ibd_count: site shards (--n_gpus > 1) are not supported yet!");
+    if (P.ibd_long_moments)
+      fatal(__FUNCTION__, "--ibd_long_moments: site shards (--n_gpus > 1) are not supported yet!");
   }
   if (P.in_ind_names) {  // the first tab- or space-separated field of each line (convert_ibd.pl --ind)
     gzFile fh = gzopen(P.in_ind_names, "r");
@@ -2668,8 +2774,8 @@ void parse_cmd_args(Params& P, int argc, char** argv) {  // parse_args.cpp:41-22
       fatal(__FUNCTION__, "number of lines in --ind_names file is not --n_ind!");
     if (!P.ibd_bed && !P.sample_paths && !P.indF_se && !P.ibd_summary && !P.ibd_sharing && !P.ibd_support &&
         !P.ibd_bounds && !P.geno_summary && !P.ibd_expect && !P.ibd_moments && !P.ibd_by_length &&
-        !P.ibd_longest && !P.ibd_long && !P.ibd_count)
-      warn(__FUNCTION__, "--ind_names is only used by --ibd_bed, --sample_paths, --indF_se, --ibd_summary, --ibd_sharing, --ibd_support, --ibd_bounds, --geno_summary, --ibd_expect, --ibd_moments, --ibd_by_length, --ibd_longest, --ibd_long and --ibd_count");
+        !P.ibd_longest && !P.ibd_long && !P.ibd_count && !P.ibd_long_moments)
+      warn(__FUNCTION__, "--ind_names is only used by --ibd_bed, --sample_paths, --indF_se, --ibd_summary, --ibd_sharing, --ibd_support, --ibd_bounds, --geno_summary, --ibd_expect, --ibd_moments, --ibd_by_length, --ibd_longest, --ibd_long, --ibd_count and --ibd_long_moments");
   }
   P.prefix = P.out_prefix;
 }
@@ -2776,6 +2882,7 @@ void finish_run(Params& P, Cohort& C) {
   if (P.ibd_longest) write_ibd_longest(P, C);
   if (P.ibd_long) write_ibd_long(P, C);
   if (P.ibd_count) write_ibd_count(P, C);
+  if (P.ibd_long_moments) write_ibd_long_moments(P, C);
   if (P.verbose >= 2)  // (not a line of the reference's)
     fprintf(P.out, "> decoded in %.2f s, output files written in %.2f s\n", t1 - t0, omp_get_wtime() - t1);
 }
@@ -2902,6 +3009,7 @@ int main(int argc, char** argv) {
         runs[r].ibd_longest = P.ibd_longest && r == best;
         runs[r].ibd_long = P.ibd_long && r == best;
         runs[r].ibd_count = P.ibd_count && r == best;
+        runs[r].ibd_long_moments = P.ibd_long_moments && r == best;
         finish_run(runs[r], cs[r]);
       }
       fclose(runs[r].out);
@@ -2940,6 +3048,7 @@ int main(int argc, char** argv) {
         if (P.long_post) exts.push_back(".ibd.long.post");
       }
       if (P.ibd_count) exts.push_back(".ibd.count");
+      if (P.ibd_long_moments) exts.push_back(".ibd.long.moments");
       for (unsigned k = 1; P.sample_paths && k <= P.sample_keep; k++) {
         char tag[32];
         snprintf(tag, sizeof tag, ".sample_%02u.ibd", k);

@@ -178,6 +178,7 @@ def load_library():
         "nghmm_chain_ibd_longest": (i32, [C.POINTER(vp), i32, i32, u32, dp, u64, C.POINTER(u64),
                                           C.POINTER(u64), vp]),
         "nghmm_ibd_count": (i32, [vp, i32, u32, dp, u32, u64, C.POINTER(u64), C.POINTER(u64), dp]),
+        "nghmm_ibd_long_moments": (i32, [vp, i32, u32, dp, u64, C.POINTER(u64), C.POINTER(u64), vp]),
         "nghmm_ibd_long": (i32, [vp, i32, u32, dp, d, u64, C.POINTER(u64), C.POINTER(u64), vp, vp, dp]),
         "nghmm_chain_ibd_long": (i32, [C.POINTER(vp), i32, i32, u32, dp, d, u64, C.POINTER(u64),
                                        C.POINTER(u64), vp, vp, dp]),
@@ -231,6 +232,7 @@ EXPORTED_SYMBOLS = [
     "nghmm_ibd_longest", "nghmm_chain_ibd_longest",
     "nghmm_ibd_long",
     "nghmm_ibd_count",
+    "nghmm_ibd_long_moments",
 ]
 # (nghmm_chain_ibd_long is declared in include/nghmm_chain_long.h)
 
@@ -839,6 +841,34 @@ def count_summary(prob, levels=(0.025, 0.5, 0.975)):
     q = (cum[..., None, :] < lv[:, None]).sum(axis=-1).astype(np.int64)
     return {"mean_lower": (p * np.arange(M + 1)).sum(axis=-1), "p_more": p[..., M].copy(),
             "mode": np.argmax(p, axis=-1).astype(np.int64), "quantiles": q}
+
+
+LONG_MOMENTS_MB = 1    # nghmm_ibd_long_moments: thresholds and lengths in Mb instead of sites
+
+
+class LongMomentStat(C.Structure):   # nghmm_long_moment_stat (include/nghmm.h)
+    _fields_ = [(n, C.c_double) for n in ("mean_a", "mean_t", "var_a", "cov_at", "var_t")]
+
+
+LONG_MOMENT_DTYPE = np.dtype([(n, np.float64) for n, _ in LongMomentStat._fields_])
+assert LONG_MOMENT_DTYPE.itemsize == C.sizeof(LongMomentStat) == 40
+
+
+def long_moment_sd(stats, total=None):
+    """What ibd_long_moments' records say about uncertainty, as a dict of arrays of stats' shape:
+    moment_sd's sd_a, sd_t, corr (NaN where a variance is 0), tract_length = mean_a / mean_t and
+    tract_length_sd, its delta-method posterior sd (both NaN where mean_t is 0); and with total --
+    the sites or Mb of the region, a number or an array that broadcasts against stats -- share =
+    mean_a / total (F_ROH above the threshold) and share_sd = sd_a / total (NaN where total is
+    0)."""
+    out = moment_sd(stats)
+    if total is not None:
+        tot = np.broadcast_to(np.asarray(total, dtype=np.float64), out["sd_a"].shape)
+        for name, src in (("share", np.asarray(stats["mean_a"], dtype=np.float64)), ("share_sd", out["sd_a"])):
+            v = np.full(tot.shape, np.nan)
+            np.divide(src, tot, out=v, where=tot != 0)
+            out[name] = v
+    return out
 
 
 LONG_MB = 1            # nghmm_ibd_long: thresholds in Mb instead of sites
@@ -1516,6 +1546,18 @@ class NgsFHMM:
                                              end.ctypes.data_as(u64p) if R else None,
                                              _dp(prob) if R and K else None))
         return prob
+
+    def ibd_long_moments(self, min_len, unit="sites", regions=None):
+        """Exact posterior mean and covariance of (total length, number) of the long IBD runs
+        (nghmm_ibd_long_moments): [I][R][K] of LONG_MOMENT_DTYPE -- mean_a and var_a of the sites
+        (Mb with unit="mb") of the region inside IBD runs of at least min_len[k], mean_t and var_t
+        of the number of such runs, and cov_at.  min_len, unit and regions as ibd_count takes them;
+        a run is cut at chromosome starts and at the region's edges.  Conditional on indF, alpha
+        and the frequencies; long_moment_sd turns the records into standard deviations and the
+        share of a region."""
+        return _ibd_by_length(lambda *a: self.lib.nghmm_ibd_long_moments(self._h, *a), self._check,
+                              self.n_ind, self.n_sites, min_len, unit, regions, LONG_MOMENT_DTYPE,
+                              "ibd_long_moments", LONG_MOMENTS_MB)
 
     def ibd_long(self, min_len, unit="sites", regions=None, sites=True, post=False, threshold=0.5):
         """The posterior of every site of lying in an IBD tract of at least min_len[k], exactly
